@@ -29,6 +29,12 @@ Timing contract: W untimed warm-up steps; barrier + device sync; K timed steps (
 forward + backward + gradient sync + optimizer step over fresh data); barrier + device sync;
 the MAX elapsed over ranks; rank 0 prints one JSON line.
 
+A plain run does only that (at N > 1 it also checks that the replicas still agree: a figure from diverged
+replicas is no result, exit 3). ``--dump-outputs DIR`` also writes what the last timed step returned and the
+parameters it left behind as ``DIR/<name>.npy`` (seeded data and weights: the same arguments give the same
+inputs). ``--full`` adds what the headline figure does not need: at even N the reference's placement (pp2dp)
+timed next to the chosen one.
+
     python bench.py --gpus 1 --steps 50 --warmup 10
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --steps 50 --warmup 10
 """
@@ -98,9 +104,15 @@ def parse():
                    help="pp2dp: pipeline schedule (default chimera)")
     p.add_argument("--dataset_batches", type=int, default=4, help="distinct batches cycled through")
     p.add_argument("--model", default="mlp")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what the headline figure does not need: the reference's "
+                        "placement (pp2dp) timed next to the chosen one at even N (--alternatives)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step returned (loss_sum, correct, count) and "
+                        "the parameters it left behind as DIR/<name>.npy")
     p.add_argument("--alternatives", default="auto", choices=["auto", "on", "off"],
                    help="after the timed steps, also time the reference's placement (pp2dp) for the JSON; "
-                        "auto: at every even N (the reference's cut at 2, 4, 8 GPUs)")
+                        "auto: with --full at every even N (the reference's cut at 2, 4, 8 GPUs)")
     p.add_argument("--link_probe", default="auto", choices=["auto", "on", "off"],
                    help="N > 1: measure the all-reduce / all-to-all / pair exchange on the job's process group before "
                         "choosing the placement, and feed the measured link model to it (parallel/linkprobe.py)")
@@ -221,6 +233,33 @@ def _replica_check(engine, mesh, dev, rank):
     same = all(int(lo[2 * s + j]) == int(hi[2 * s + j]) for s in held for j in range(2))
     return {"identical": bool(same), "stages_checked": held,
             "checksums": {str(s): [int(lo[2 * s]), int(lo[2 * s + 1])] for s in held}}
+
+
+DUMP_MAX_BYTES = 60 * 2 ** 20  # all ranks together stay under 64 MB
+
+
+def _dump_outputs(path, res, engine, rank, world):
+    """``--dump-outputs DIR``: what a caller of the timed step holds after the last one, as ``DIR/<name>.npy``: the
+    StepResult it returned (``loss_sum``, ``correct`` float32; ``count`` float64) and the flat parameters the step left
+    in the engine (``params``, float32; a fixed seeded sample of them if they would not fit the size limit). At N > 1
+    every rank writes its own as ``<name>.rank<r>.npy``. Data, initial weights and the sample are seeded, so two builds
+    run with the same arguments can be compared array for array."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    p = engine.parameters_vector().reshape(-1).float().cpu().numpy()
+    arrays = {}
+    keep = DUMP_MAX_BYTES // (4 * world)
+    if p.size > keep:
+        p = p[np.sort(np.random.default_rng(0).choice(p.size, keep, replace=False))]
+    arrays["params"] = p
+    if res is not None:
+        arrays["loss_sum"] = res.loss_sum.detach().float().cpu().numpy().reshape(1)
+        arrays["correct"] = res.correct.detach().float().cpu().numpy().reshape(1)
+        arrays["count"] = np.array([res.count], dtype=np.float64)
+    suffix = "" if world == 1 else f".rank{rank}"
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), arr)
 
 
 def main():
@@ -376,15 +415,17 @@ def main():
         engine.transport.all_reduce(sent, channel="world", async_op=False)
     el = float(t.item())
     cross_bytes = float(sent.item()) / a.steps
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, res, engine, rank, world)
     replicas = _replica_check(engine, mesh, dev, rank) if world > 1 else None
     loss = None
     if res is not None:
         l, c, cnt = engine.reduce_metrics(res)
         loss = l / max(1, cnt)
     sps = GB * a.steps / el
-    # the reference's own placement, measured next to the chosen one (after the timed region)
+    # --full: the reference's own placement, measured next to the chosen one (after the timed region)
     alternatives = {}
-    want_alt = a.alternatives == "on" or (a.alternatives == "auto" and n % 2 == 0)
+    want_alt = a.alternatives == "on" or (a.full and a.alternatives == "auto" and n % 2 == 0)
     if want_alt and n > 1 and n % 2 == 0 and place != "pp2dp" and a.model == "mlp":
         try:
             alternatives["pp2dp"] = _measure_pp2dp(a, n, rank, world, dev)

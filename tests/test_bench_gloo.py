@@ -40,6 +40,7 @@ def _run(world, extra=()):
     d = json.loads(lines[0])
     assert d["n_gpus"] == world and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == world * 256 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["ms_per_step"] == pytest.approx(world * 256 / d["value"] * 1e3, rel=1e-2)
     assert d["final_loss"] is not None and d["final_loss"] == d["final_loss"]  # finite
     assert d["config"]["world_size_seen"] == world and d["config"]["backend"] == "gloo"
     # self-checks of a multi-rank run: replicas bit-identical after the timed steps, links measured before the
@@ -95,13 +96,52 @@ def test_bench_gpus_flag_spawns_ranks_on_cpu(tmp_path):
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_bench_measures_the_reference_placement_at_every_even_n(world):
-    """At every even N the JSON also carries a measured pp2dp step (stage 0 | stage 1 on the GPUs of each pair,
-    Chimera, factored boundary gradient: 512 + 40 B per row over the link), next to the placement the measured
-    link model chose."""
-    d = _run(world, ["--placement", "dp"])
+    """At every even N the JSON of a ``--full`` run also carries a measured pp2dp step (stage 0 | stage 1 on the GPUs
+    of each pair, Chimera, factored boundary gradient: 512 + 40 B per row over the link), next to the placement the
+    measured link model chose."""
+    d = _run(world, ["--full", "--placement", "dp"])
     alt = d["config"]["measured_alternatives"]["pp2dp"]
     assert "error" not in alt, alt
     assert alt["samples_per_s"] > 0 and alt["boundary_bytes_across_gpus_per_step"] == world * 256 * (512 + 40)
+
+
+def test_bench_plain_run_leaves_the_extras_to_full():
+    """Without ``--full`` a multi-rank run times no second placement after the headline (``--alternatives on`` still
+    asks for that one explicitly)."""
+    d = _run(2, ["--placement", "dp"])
+    assert d["config"]["measured_alternatives"] == {}
+    d = _run(2, ["--placement", "dp", "--alternatives", "on"])
+    assert d["config"]["measured_alternatives"]["pp2dp"]["samples_per_s"] > 0
+
+
+def test_bench_dump_outputs_repeat_exactly(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's result and the parameters it left, as float32/float64 ``.npy``;
+    seeded data and weights, so a second run with the same arguments writes the same arrays (the CPU path is
+    deterministic) and a run with one more step does not."""
+    import subprocess
+
+    import numpy as np
+
+    env = dict(os.environ, SDML_BENCH_BATCH="256", PYTHONPATH=ROOT)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    got = {}
+    for name, steps in (("a", 2), ("b", 2), ("c", 3)):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+               "--dump-outputs", str(tmp_path / name)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        got[name] = {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+        assert d["final_loss"] == pytest.approx(float(got[name]["loss_sum"][0]) / 256, abs=1e-5)
+    assert set(got["a"]) == {"loss_sum", "correct", "count", "params"}
+    assert all(v.dtype in (np.float32, np.float64) for v in got["a"].values())
+    assert got["a"]["count"][0] == 256 and got["a"]["params"].size >= 784 * 128 + 128 + 128 * 10 + 10
+    assert sum(v.nbytes for v in got["a"].values()) <= 64 * 2 ** 20
+    for k, v in got["a"].items():
+        assert np.array_equal(v, got["b"][k]), k
+    assert not np.array_equal(got["a"]["params"], got["c"]["params"])
 
 
 def test_bench_exits_nonzero_when_replicas_diverge():

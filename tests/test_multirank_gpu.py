@@ -161,7 +161,7 @@ def test_bench_two_ranks_on_one_gpu():
     for place, cross, tr in (("rotate", True, "host"), ("auto", None, "host"), ("rotate", True, "ipc")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
-               "--gpus", "2", "--steps", "3", "--warmup", "1", "--placement", place]
+               "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--placement", place]
         r = subprocess.run(cmd, env=dict(env, SDML_TRANSPORT=tr), capture_output=True, text=True, timeout=300,
                            cwd=ROOT)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
