@@ -56,7 +56,20 @@ def add_engine_args(parser: argparse.ArgumentParser):
     g.add_argument("--epochs", type=int, default=10)
     g.add_argument("--lr", type=float, default=0.1)
     g.add_argument("--momentum", type=float, default=0.5)
-    g.add_argument("--weight_decay", type=float, default=0.0)
+    g.add_argument("--weight_decay", type=float, default=0.0,
+                   help="sgd: L2 term on every parameter; adamw: decoupled, parameters with dim >= 2 only")
+    g.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"])
+    g.add_argument("--beta1", type=float, default=0.9, help="adamw")
+    g.add_argument("--beta2", type=float, default=0.999, help="adamw")
+    g.add_argument("--eps", type=float, default=1e-8, help="adamw")
+    g.add_argument("--clip_grad", type=float, default=0.0,
+                   help="adamw: clip the gradient to this global norm (0: off)")
+    g.add_argument("--lr_schedule", default="constant", choices=["constant", "cosine"],
+                   help="after --warmup_steps of linear warmup: constant --lr, or cosine decay to --min_lr at "
+                        "--lr_decay_steps")
+    g.add_argument("--warmup_steps", type=int, default=0)
+    g.add_argument("--lr_decay_steps", type=int, default=0, help="cosine: the step at which --min_lr is reached")
+    g.add_argument("--min_lr", type=float, default=0.0)
     g.add_argument("--log_interval", type=int, default=10)
     g.add_argument("--data", default="auto", choices=["auto", "synthetic", "random", "mnist"],
                    help="auto: MNIST idx files under --data_dir if present, else synthetic")
@@ -118,8 +131,25 @@ def export_env(args) -> None:
                       "the libraries (pass --interface lo for single-host runs)")
 
 
+def lr_schedule_of(args):
+    """The --lr_schedule / --warmup_steps / --lr_decay_steps / --min_lr flags as the engine takes them (None: the
+    learning rate never changes)."""
+    from .ops.optim import make_schedule
+
+    return make_schedule(args.lr_schedule, args.warmup_steps, args.lr_decay_steps, args.min_lr)
+
+
 def parse_args(argv: Optional[List[str]] = None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.warmup_steps < 0 or args.lr_decay_steps < 0:
+        parser.error("--warmup_steps and --lr_decay_steps must be >= 0")
+    if args.clip_grad and args.optimizer != "adamw":
+        parser.error("--clip_grad needs --optimizer adamw")
+    if args.graph and args.optimizer == "sgd" and (args.lr_schedule != "constant" or args.warmup_steps > 0):
+        parser.error("--graph with --optimizer sgd and a learning-rate schedule: the SGD step takes lr as a launch "
+                     "argument, which a captured graph freezes; use --optimizer adamw (its schedule runs on the "
+                     "device) or drop --graph")
     if args.rank is None and "RANK" in os.environ:
         args.rank = int(os.environ["RANK"])
     if args.world_size is None:

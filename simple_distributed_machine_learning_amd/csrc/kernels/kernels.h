@@ -247,6 +247,33 @@ void sgd_momentum(float* p, float* g, float* buf, int64_t n, float lr, float mom
 void sgd_momentum_mixed(float* master, void* p_bf16, void* g_bf16, float* buf, int64_t n, float lr, float momentum,
                         float dampening, float wd, bool nesterov, bool first, bool zero_grad, hipStream_t stream);
 
+// ---- AdamW with global-norm clipping and a device-side schedule (adamw.hip, adamw_rule.h) -----------------------
+// sum g^2 over n elements (fp32: n % 4 == 0, bf16: n % 8 == 0, 16-B aligned): per-block fp32 partials
+// (grad_sqnorm_blocks(n, bf16) <= kGradSqnormMaxBlocks of them; returned), then a fixed-order fp64 sum. Deterministic.
+constexpr int kGradSqnormMaxBlocks = 2048;
+constexpr int kAdamwPrepFloats = 8;  // the prep block (adamw_rule.h AdamwPrepSlot)
+int grad_sqnorm_blocks(int64_t n, bool bf16);
+int grad_sqnorm_partials(const void* g, int64_t n, bool bf16, float* partials, hipStream_t stream);
+void grad_sqnorm_finish(const float* partials, int nparts, double* out, hipStream_t stream);
+// the step's scalars, computed on the device from the step counter (advanced here) and the squared norm
+struct AdamwSchedule {
+  double lr, b1, b2;
+  double max_norm;              // <= 0: clipping off (c = 1, the norm is not read)
+  double min_lr;
+  int64_t warmup, decay_steps;  // lr_t = lr t / warmup for t <= warmup; cosine to min_lr at decay_steps
+  int cosine;
+};
+// partials != nullptr: sums them first (the finish fused in) and stores the total in norm2 (if non-null); else reads
+// the total from norm2 (nullptr: no norm). prep: kAdamwPrepFloats floats (adamw_rule.h).
+void adamw_prep(const float* partials, int nparts, double* norm2, int64_t* step_ctr, float* prep,
+                const AdamwSchedule& sched, hipStream_t stream);
+// one pass; decay: one byte per 64-element granule (ceil(n / 64) of them); zero_grad: also clears g
+void adamw(float* p, float* g, float* m, float* v, const unsigned char* decay, const float* prep, int64_t n, double b1,
+           double b2, double eps, double wd, bool zero_grad, hipStream_t stream);
+void adamw_mixed(float* master, void* p_bf16, void* g_bf16, float* m, float* v, const unsigned char* decay,
+                 const float* prep, int64_t n, double b1, double b2, double eps, double wd, bool zero_grad,
+                 hipStream_t stream);
+
 // ---- synthetic MNIST-shape data (counter-based; bit-identical to the host generator) -----
 void synth_mnist(uint64_t seed, int64_t start, int64_t n, int H, int W, int mode, float* x, int64_t* y,
                  hipStream_t stream);

@@ -1524,6 +1524,112 @@ void sgd_momentum_mixed_(torch::Tensor master, torch::Tensor p, torch::Tensor g,
                            cur_stream());
 }
 
+// ---- AdamW (adamw.hip): every argument is checked here, so a wrong call raises instead of reaching a kernel -------
+bool aligned16(const torch::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0; }
+
+void check_dev_vec(const torch::Tensor& t, torch::ScalarType dt, const torch::Tensor& like, const char* op,
+                   const char* name) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a ROCm device tensor");
+  TORCH_CHECK(t.scalar_type() == dt, op, ": ", name, " must be ", c10::toString(dt));
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+  TORCH_CHECK(t.device() == like.device(), op, ": ", name, " is on another device");
+  TORCH_CHECK(aligned16(t), op, ": ", name, " must be 16-B aligned");
+}
+
+// the gradient buffer of grad_sqnorm / the update kernels: fp32 (n % 4 == 0) or bf16 (n % 8 == 0)
+bool check_grads(const torch::Tensor& g, const char* op) {
+  TORCH_CHECK(g.scalar_type() == torch::kFloat32 || g.scalar_type() == torch::kBFloat16, op,
+              ": gradients must be float32 or bfloat16");
+  const bool bf16 = g.scalar_type() == torch::kBFloat16;
+  check_dev_vec(g, g.scalar_type(), g, op, "g");
+  TORCH_CHECK(g.numel() % (bf16 ? 8 : 4) == 0, op, ": numel must be a multiple of ", bf16 ? 8 : 4);
+  return bf16;
+}
+
+int64_t grad_sqnorm_blocks_op(int64_t n, bool bf16) { return sdml::grad_sqnorm_blocks(n, bf16); }
+
+// partials: fp32 [>= grad_sqnorm_blocks]; out: fp64 [1] = sum g^2
+void grad_sqnorm_op(torch::Tensor g, torch::Tensor partials, torch::Tensor out) {
+  const bool bf16 = check_grads(g, "grad_sqnorm");
+  check_dev_vec(partials, torch::kFloat32, g, "grad_sqnorm", "partials");
+  check_dev_vec(out, torch::kFloat64, g, "grad_sqnorm", "out");
+  TORCH_CHECK(partials.numel() >= sdml::grad_sqnorm_blocks(g.numel(), bf16), "grad_sqnorm: partials too short");
+  TORCH_CHECK(out.numel() == 1, "grad_sqnorm: out must hold one fp64 scalar");
+  const int nb = sdml::grad_sqnorm_partials(g.data_ptr(), g.numel(), bf16, partials.data_ptr<float>(), cur_stream());
+  sdml::grad_sqnorm_finish(partials.data_ptr<float>(), nb, out.data_ptr<double>(), cur_stream());
+}
+
+// g given: sum g^2 (partials; the finish is fused into the prep launch) -> norm2; g absent: norm2 (if given) already
+// holds the total (summed across ranks by the caller). Writes prep [8] fp32 and advances step_ctr (int64 [1]).
+void adamw_prep_op(c10::optional<torch::Tensor> g, c10::optional<torch::Tensor> partials,
+                   c10::optional<torch::Tensor> norm2, torch::Tensor step_ctr, torch::Tensor prep, double lr, double b1,
+                   double b2, double max_norm, bool cosine, int64_t warmup, int64_t decay_steps, double min_lr) {
+  check_dev_vec(prep, torch::kFloat32, prep, "adamw_prep", "prep");
+  check_dev_vec(step_ctr, torch::kInt64, prep, "adamw_prep", "step_ctr");
+  TORCH_CHECK(prep.numel() == sdml::kAdamwPrepFloats, "adamw_prep: prep must hold ", sdml::kAdamwPrepFloats, " floats");
+  TORCH_CHECK(step_ctr.numel() == 1, "adamw_prep: step_ctr must hold one int64");
+  TORCH_CHECK(b1 >= 0 && b1 < 1 && b2 >= 0 && b2 < 1 && warmup >= 0 && decay_steps >= 0, "adamw_prep: betas in [0, 1), "
+              "warmup and decay_steps >= 0");
+  double* n2 = nullptr;
+  if (norm2.has_value() && norm2->defined()) {
+    check_dev_vec(*norm2, torch::kFloat64, prep, "adamw_prep", "norm2");
+    TORCH_CHECK(norm2->numel() == 1, "adamw_prep: norm2 must hold one fp64 scalar");
+    n2 = norm2->data_ptr<double>();
+  }
+  TORCH_CHECK(max_norm <= 0 || n2 != nullptr, "adamw_prep: clipping needs norm2");
+  const sdml::AdamwSchedule s{lr, b1, b2, max_norm, min_lr, warmup, decay_steps, cosine ? 1 : 0};
+  const float* parts = nullptr;
+  int nb = 0;
+  if (g.has_value() && g->defined()) {
+    const bool bf16 = check_grads(*g, "adamw_prep");
+    TORCH_CHECK(partials.has_value() && partials->defined(), "adamw_prep: g needs the partials workspace");
+    check_dev_vec(*partials, torch::kFloat32, prep, "adamw_prep", "partials");
+    TORCH_CHECK(g->device() == prep.device(), "adamw_prep: g is on another device");
+    TORCH_CHECK(partials->numel() >= sdml::grad_sqnorm_blocks(g->numel(), bf16), "adamw_prep: partials too short");
+    TORCH_CHECK(n2 != nullptr, "adamw_prep: g needs norm2");
+    nb = sdml::grad_sqnorm_partials(g->data_ptr(), g->numel(), bf16, partials->data_ptr<float>(), cur_stream());
+    parts = partials->data_ptr<float>();
+  }
+  sdml::adamw_prep(parts, nb, n2, step_ctr.data_ptr<int64_t>(), prep.data_ptr<float>(), s, cur_stream());
+}
+
+void check_adamw_common(const torch::Tensor& ref, const torch::Tensor& m, const torch::Tensor& v,
+                        const torch::Tensor& decay, const torch::Tensor& prep, const char* op) {
+  check_dev_vec(m, torch::kFloat32, ref, op, "m");
+  check_dev_vec(v, torch::kFloat32, ref, op, "v");
+  check_dev_vec(decay, torch::kUInt8, ref, op, "decay");
+  check_dev_vec(prep, torch::kFloat32, ref, op, "prep");
+  TORCH_CHECK(m.numel() == ref.numel() && v.numel() == ref.numel(), op, ": m / v size mismatch");
+  TORCH_CHECK(decay.numel() == (ref.numel() + 63) / 64, op, ": the decay table must have one entry per 64 elements (",
+              (ref.numel() + 63) / 64, "), got ", decay.numel());
+  TORCH_CHECK(prep.numel() == sdml::kAdamwPrepFloats, op, ": prep must hold ", sdml::kAdamwPrepFloats, " floats");
+}
+
+void adamw_(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, torch::Tensor decay,
+            torch::Tensor prep, double b1, double b2, double eps, double wd, bool zero_grad) {
+  check_dev_vec(p, torch::kFloat32, p, "adamw", "p");
+  check_dev_vec(g, torch::kFloat32, p, "adamw", "g");
+  TORCH_CHECK(p.numel() == g.numel(), "adamw: p / g size mismatch");
+  TORCH_CHECK(p.numel() % 4 == 0, "adamw: numel must be a multiple of 4");
+  check_adamw_common(p, m, v, decay, prep, "adamw");
+  sdml::adamw(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+              decay.data_ptr<uint8_t>(), prep.data_ptr<float>(), p.numel(), b1, b2, eps, wd, zero_grad, cur_stream());
+}
+
+void adamw_mixed_(torch::Tensor master, torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v,
+                  torch::Tensor decay, torch::Tensor prep, double b1, double b2, double eps, double wd,
+                  bool zero_grad) {
+  check_dev_vec(master, torch::kFloat32, master, "adamw_mixed", "master");
+  check_dev_vec(p, torch::kBFloat16, master, "adamw_mixed", "p");
+  check_dev_vec(g, torch::kBFloat16, master, "adamw_mixed", "g");
+  TORCH_CHECK(p.numel() == master.numel() && g.numel() == master.numel(), "adamw_mixed: master / p / g size mismatch");
+  TORCH_CHECK(master.numel() % 8 == 0, "adamw_mixed: numel must be a multiple of 8");
+  check_adamw_common(master, m, v, decay, prep, "adamw_mixed");
+  sdml::adamw_mixed(master.data_ptr<float>(), p.data_ptr(), g.data_ptr(), m.data_ptr<float>(), v.data_ptr<float>(),
+                    decay.data_ptr<uint8_t>(), prep.data_ptr<float>(), master.numel(), b1, b2, eps, wd, zero_grad,
+                    cur_stream());
+}
+
 void synth_mnist(int64_t seed, int64_t start, int64_t n, int64_t H, int64_t W, int64_t mode, torch::Tensor x,
                  torch::Tensor y) {
   check_f32_cuda(x, "x");
@@ -1950,6 +2056,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("planes") = py::none(), py::arg("plane_offset") = 0, py::arg("plane_rows") = 0,
         py::arg("plane_k") = 0);
   m.def("sgd_momentum_mixed_", &sgd_momentum_mixed_, "SGD: fp32 master + momentum, bf16 grads/params");
+  m.def("grad_sqnorm_blocks", &grad_sqnorm_blocks_op, "blocks (= fp32 partials) grad_sqnorm launches for n elements");
+  m.def("grad_sqnorm", &grad_sqnorm_op, "sum g^2 over a flat fp32 / bf16 buffer -> one fp64 scalar (deterministic)");
+  m.def("adamw_prep", &adamw_prep_op, "AdamW step scalars on the device: schedule, bias corrections, clip coefficient",
+        py::arg("g"), py::arg("partials"), py::arg("norm2"), py::arg("step_ctr"), py::arg("prep"), py::arg("lr"),
+        py::arg("b1"), py::arg("b2"), py::arg("max_norm"), py::arg("cosine"), py::arg("warmup"),
+        py::arg("decay_steps"), py::arg("min_lr"));
+  m.def("adamw_", &adamw_, "AdamW over a flat fp32 buffer (step scalars from the prep block)");
+  m.def("adamw_mixed_", &adamw_mixed_, "AdamW: fp32 master + moments, bf16 grads/params");
   m.def("cross_entropy_bf16", &cross_entropy_bf16, "vocab cross-entropy on bf16 logits (+ dlogits)");
   m.def("layernorm_fwd_bf16", &layernorm_fwd_bf16, "LayerNorm forward (bf16, fp32 stats)");
   m.def("layernorm_bwd_bf16", &layernorm_bwd_bf16, "LayerNorm backward (bf16)");

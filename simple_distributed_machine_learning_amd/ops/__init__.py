@@ -405,6 +405,91 @@ def sgd_momentum_mixed_(master, p, g, buf, lr: float, momentum: float, dampening
         g.zero_()
 
 
+# ---- AdamW with global-norm clipping and a device-side schedule (csrc/kernels/adamw.hip) ----------
+ADAMW_PREP_FLOATS = 8  # the prep block: t, lr_t, c, lr_t / (1 - b1^t), 1 / sqrt(1 - b2^t), norm, 2 unused
+PREP_T, PREP_LR, PREP_CLIP, PREP_STEP, PREP_RBC2, PREP_NORM = range(6)
+SQNORM_MAX_BLOCKS = 2048  # grad_sqnorm's grid cap = the most fp32 partials it writes
+DECAY_GRANULE = 64  # elements per decay-table entry (= utils.flat.ALIGN)
+
+
+def grad_sqnorm_geometry(n: int, bf16: bool):
+    """(blocks, threads per block, elements per lane and trip) of the grad_sqnorm launch for ``n`` elements: the
+    grid stride is their product."""
+    return int(_k().grad_sqnorm_blocks(int(n), bool(bf16))), 256, 8 if bf16 else 4
+
+
+def grad_sqnorm(g, out=None, partials=None):
+    """Sum of g^2 over a flat fp32 / bf16 buffer as one float64 scalar (``out``, shape [1]). Deterministic."""
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=g.device)
+    if g.is_cuda:
+        if partials is None:
+            partials = torch.empty(SQNORM_MAX_BLOCKS, dtype=torch.float32, device=g.device)
+        _k().grad_sqnorm(g, partials, out)
+    else:
+        out.copy_(ref.grad_sqnorm(g))
+    return out
+
+
+def adamw_prep(step_ctr, prep, lr: float, beta1: float, beta2: float, max_norm: float = 0.0, schedule=None,
+               g=None, partials=None, norm2=None):
+    """The step's scalars -> ``prep``; advances ``step_ctr`` (int64 [1]). With ``g``: its squared norm is summed here
+    (into ``norm2``); without: ``norm2`` already holds the total (or clipping is off). ``schedule``: None or
+    {"kind", "warmup", "decay_steps", "min_lr"} (reference.lr_at). On CPU ``prep`` is float64."""
+    s = schedule or {}
+    kind, warmup = s.get("kind", "constant"), int(s.get("warmup", 0))
+    decay_steps, min_lr = int(s.get("decay_steps", 0)), float(s.get("min_lr", 0.0))
+    if step_ctr.is_cuda:
+        _k().adamw_prep(g, partials, norm2, step_ctr, prep, float(lr), float(beta1), float(beta2), float(max_norm),
+                        kind == "cosine", warmup, decay_steps, min_lr)
+        return
+    if g is not None:
+        norm2.copy_(ref.grad_sqnorm(g))
+    t = int(step_ctr[0]) + 1
+    lr_t = ref.lr_at(t, lr, warmup, decay_steps, min_lr, kind)
+    clipping = max_norm > 0
+    prep[PREP_T], prep[PREP_LR] = t, lr_t
+    prep[PREP_CLIP] = ref.clip_coef(norm2[0], max_norm) if clipping else 1.0
+    prep[PREP_STEP] = lr_t / (1.0 - beta1 ** t)
+    prep[PREP_RBC2] = 1.0 / (1.0 - beta2 ** t) ** 0.5
+    prep[PREP_NORM] = norm2[0].sqrt() if clipping else 0.0
+    step_ctr[0] = t
+
+
+def _cpu_adamw(p32, g, m, v, decay, prep, beta1, beta2, eps, weight_decay):
+    wd = 0.0
+    if weight_decay != 0:
+        wd = decay.repeat_interleave(DECAY_GRANULE)[:p32.numel()].to(torch.float32) * weight_decay
+    ref.adamw_(p32, g.float(), m, v, int(prep[PREP_T]), float(prep[PREP_LR]), beta1, beta2, eps, wd,
+               float(prep[PREP_CLIP]))
+
+
+def adamw_(p, g, m, v, decay, prep, beta1: float, beta2: float, eps: float, weight_decay: float,
+           zero_grad: bool = False):
+    """AdamW step on flat fp32 buffers with the scalars of ``prep`` (adamw_prep); ``decay``: uint8, one entry per
+    64 elements (1: decayed). With ``zero_grad`` the kernel also clears ``g``."""
+    if p.is_cuda:
+        _k().adamw_(p, g, m, v, decay, prep, float(beta1), float(beta2), float(eps), float(weight_decay),
+                    bool(zero_grad))
+        return
+    _cpu_adamw(p, g, m, v, decay, prep, beta1, beta2, eps, weight_decay)
+    if zero_grad:
+        g.zero_()
+
+
+def adamw_mixed_(master, p, g, m, v, decay, prep, beta1: float, beta2: float, eps: float, weight_decay: float,
+                 zero_grad: bool = False):
+    """AdamW on fp32 ``master`` weights and moments from bf16 grads ``g``; writes ``p`` = bf16(master)."""
+    if master.is_cuda:
+        _k().adamw_mixed_(master, p, g, m, v, decay, prep, float(beta1), float(beta2), float(eps),
+                          float(weight_decay), bool(zero_grad))
+        return
+    _cpu_adamw(master, g, m, v, decay, prep, beta1, beta2, eps, weight_decay)
+    p.copy_(master)
+    if zero_grad:
+        g.zero_()
+
+
 # ---- reference CNN: one launch per stage pass (csrc/kernels/ref_cnn.hip) --------------------
 # Dropout seeds: ``seed`` (host, per pass) combined with ``ctr`` (optional int64 device step
 # counter, advanced inside captured hipGraphs) as ops.reference.effective_seed.

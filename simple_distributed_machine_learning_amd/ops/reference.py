@@ -5,6 +5,7 @@ what the numerics tests compare against. They also serve the CPU (Gloo) path.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -73,6 +74,62 @@ def sgd_momentum_(p, g, buf, lr: float, momentum: float, dampening: float = 0.0,
             buf.mul_(momentum).add_(d, alpha=1 - dampening)
         d = d + momentum * buf if nesterov else buf
     p.add_(d, alpha=-lr)
+
+
+CLIP_EPS = 1e-6  # torch.nn.utils.clip_grad_norm_'s: c = max_norm / (norm + 1e-6), clamped to 1
+
+
+def lr_at(step: int, lr: float, warmup: int = 0, decay_steps: int = 0, min_lr: float = 0.0,
+          kind: str = "constant") -> float:
+    """Learning rate of step ``step`` (1-based): linear warmup ``lr * step / warmup`` for ``step <= warmup``; then
+    ``lr`` (constant), or cosine decay from ``lr`` at ``warmup`` to ``min_lr`` at ``decay_steps`` and ``min_lr`` from
+    there on. A cosine schedule without a horizon (``decay_steps <= warmup``, e.g. 0) has nothing to decay over and
+    stays at ``lr``."""
+    if kind not in ("constant", "cosine"):
+        raise ValueError(f"unknown lr schedule {kind!r} (constant, cosine)")
+    t = float(step)
+    if step <= warmup:
+        return lr * t / float(warmup)
+    if kind == "cosine" and decay_steps > warmup:
+        prog = min(1.0, (t - float(warmup)) / float(decay_steps - warmup))
+        return min_lr + 0.5 * (lr - min_lr) * (1.0 + math.cos(math.pi * prog))
+    return lr
+
+
+def grad_sqnorm(g) -> torch.Tensor:
+    """Sum of squares of ``g`` as one float64 scalar tensor."""
+    return g.detach().double().pow(2).sum()
+
+
+def clip_coef(sqnorm, max_norm: float):
+    """``clip_grad_norm_``'s coefficient from the squared global norm: min(1, max_norm / (norm + 1e-6));
+    1 with clipping off (``max_norm <= 0``). float64 scalar tensor; a non-finite norm propagates."""
+    if max_norm <= 0:
+        return torch.ones((), dtype=torch.float64)
+    norm = torch.as_tensor(sqnorm, dtype=torch.float64).sqrt()
+    return torch.clamp(max_norm / (norm + CLIP_EPS), max=1.0)
+
+
+def adamw_(p, g, m, v, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+           weight_decay=0.0, clip: float = 1.0):
+    """torch.optim.AdamW's step ``step`` (>= 1) in place on fp32 ``p``, ``m``, ``v``, the gradient scaled by the clip
+    coefficient ``clip`` first. ``weight_decay``: a number, or a per-element tensor (``wd`` where the element belongs
+    to a decayed parameter, 0 elsewhere). ``lr`` is the step's learning rate (``lr_at``)."""
+    g = g.to(p.dtype)
+    if clip != 1.0:
+        g = g * float(clip)
+    one = torch.ones((), dtype=p.dtype)
+    lr_t = torch.tensor(lr, dtype=p.dtype)
+    if torch.is_tensor(weight_decay):
+        p.mul_(one - lr_t * weight_decay.to(p.dtype))
+    elif weight_decay != 0:
+        p.mul_(one - lr_t * torch.tensor(weight_decay, dtype=p.dtype))
+    m.mul_(beta1).add_(g, alpha=1 - beta1)
+    v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    step_size = lr / (1.0 - beta1 ** step)
+    rbc2 = 1.0 / math.sqrt(1.0 - beta2 ** step)
+    denom = v.sqrt().mul_(rbc2).add_(eps)
+    p.addcdiv_(m, denom, value=-step_size)
 
 
 def cross_entropy_fwd_bwd(logits, target, scale: float, ignore_index: int = -100):

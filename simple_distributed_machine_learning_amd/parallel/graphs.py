@@ -22,7 +22,10 @@ What changes between replays, and how it gets into the graph:
 * dropout: the fused kernels mix the engine's device step counter into their seeds. The
   graph increments that counter, so each replay draws fresh masks.
 * the optimizer: the first step (momentum-buffer initialisation) runs eagerly, so the
-  captured SGD launch is the steady-state update.
+  captured SGD launch is the steady-state update. AdamW's step number, bias corrections,
+  learning-rate schedule and clip coefficient are computed on the device from a device
+  counter that the captured launches advance (ops/optim.py FusedAdamW), so every replay
+  is the next step. SGD with a learning-rate schedule is refused (lr is a launch argument).
 
 Constraints (checked): a CUDA/ROCm engine; a training step with an optimizer update; and
 one process, unless ``allow_collectives``: RCCL collectives are captured then (the gradient
@@ -103,6 +106,10 @@ class GraphedStep:
         if engine.mesh.world_size > 1 and not allow_collectives:
             raise ValueError("GraphedStep: multi-process capture (RCCL in the graph) is opt-in: "
                              "pass allow_collectives=True")
+        if engine.optimizer.kind == "sgd" and engine.optimizer.schedule is not None:
+            # (AdamW keeps its step counter and schedule on the device: its captured step replays correctly)
+            raise ValueError("GraphedStep: the SGD step takes lr as a launch argument, which a graph freezes: a "
+                             "learning-rate schedule needs the eager step (or optimizer='adamw')")
         self.engine = engine
         self.direct = direct_data
         self.max_direct = max_direct

@@ -33,7 +33,7 @@ from ..models.base import ModelSpec, PipelineStage, build_stages
 from .. import ops
 from ..ops import pixels_to_float
 from ..ops.side_stream import join_side_streams
-from ..ops.optim import FusedSGD
+from ..ops.optim import FusedAdamW, FusedSGD
 from ..utils.flat import FlatParams
 from ..utils.timing import PhaseTimer
 from .mesh import Mesh
@@ -138,11 +138,22 @@ class PipelineEngine:
     def __init__(self, spec: ModelSpec, mesh: Mesh, schedule_kind: str = "1f1b", num_microbatches: int = 1,
                  lr: float = 0.1, momentum: float = 0.5, weight_decay: float = 0.0, seed: int = 0,
                  dtype: Optional[torch.dtype] = None, debug_sync: bool = False, timing: bool = False,
-                 cross_fraction: Optional[float] = None):
+                 cross_fraction: Optional[float] = None, optimizer: str = "sgd", betas=(0.9, 0.999),
+                 eps: float = 1e-8, clip_grad: float = 0.0, lr_schedule: Optional[dict] = None):
+        """``optimizer``: "sgd" (FusedSGD: ``momentum``) or "adamw" (FusedAdamW: ``betas``, ``eps``, ``clip_grad`` =
+        the maximum global gradient norm, 0: off). ``lr_schedule``: ops.optim.make_schedule(...) or None."""
         self.spec, self.mesh = spec, mesh
         self.kind = schedule_kind
         self.M = max(1, int(num_microbatches))
         self.P = spec.num_stages
+        if optimizer not in ("sgd", "adamw"):
+            raise ValueError(f"unknown optimizer {optimizer!r} (sgd, adamw)")
+        if clip_grad and optimizer != "adamw":
+            raise ValueError("clip_grad needs optimizer='adamw' (the SGD step has no gradient-norm pass)")
+        if clip_grad and mesh.tp > 1:
+            raise ValueError(f"clip_grad with tp={mesh.tp}: a tensor-parallel rank holds a slice of each weight and a "
+                             "replica of the rest, so no sum of the ranks' squared norms counts every parameter "
+                             "exactly once; clipping under tensor parallelism is not supported")
         if schedule_kind != "rotate" and self.P % mesh.pp != 0:
             raise ValueError(f"{spec.name}: {self.P} stages cannot be placed on {mesh.pp} pipeline ranks")
         self.device = mesh.device
@@ -184,7 +195,16 @@ class PipelineEngine:
             if getattr(m, "uses_rng_step", False):
                 m.rng_step = self.step_ctr
                 self._uses_rng = True
-        self.optimizer = FusedSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.optimizer_kind = optimizer
+        if optimizer == "adamw":
+            self.optimizer = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                        clip_grad=clip_grad, schedule=lr_schedule)
+        else:
+            self.optimizer = FusedSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay,
+                                      schedule=lr_schedule)
+        # the paths that apply the SGD rule inside another kernel (the one- / two-launch small steps, the step fused
+        # into the weight-gradient reduction) take lr as a launch argument and know no other rule
+        self._sgd_fast = optimizer == "sgd" and lr_schedule is None
         for m in self.stages.values():  # derived weight caches the step kernel keeps current
             if hasattr(m, "attach_plane_cache"):
                 m.attach_plane_cache(self.flat, self.optimizer)
@@ -193,6 +213,8 @@ class PipelineEngine:
         self.transport = mesh.transport
         self.bufs = BufferPool(self.device)
         self.grad_sync = GradSync(self.flat, mesh, self.local_stage_ids)
+        if clip_grad:
+            self._place_grad_norm(sched)
         self.training = True
         self.global_step = 0
         # rotate, 2 stages: run each wave's stage boundary as ONE all-to-all collective
@@ -239,6 +261,24 @@ class PipelineEngine:
         self._wave_bufs_retired = []
         if self.kind == "rotate" and self.P == 2 and not self.use_alltoall and mesh.pp > 1 and not mesh.p2p_groups:
             raise ValueError("rotate with p2p transfers needs a mesh built with p2p_channels=True")
+
+    def _place_grad_norm(self, sched):
+        """Where the global gradient norm comes from: every stage must be counted exactly once. A rank that holds
+        all P stages (one rank, Chimera's mirrors, rotate / dp placements) has the total in its own buffer (after the
+        gradient all-reduce, so replicas agree). With every stage on exactly one rank of the pipeline (gpipe, 1f1b)
+        the ranks' squared norms are summed over the pipeline group, stream-ordered. Anything else is refused."""
+        if len(self.local_stage_ids) == self.P:
+            return
+        owners = [{sched.stage_rank(p, s) for p in range(sched.num_pipes)} for s in range(self.P)]
+        if self.kind in ("gpipe", "1f1b") and all(len(o) == 1 for o in owners):
+            def reduce(t):
+                self.transport.all_reduce(t, channel="fwd").wait()
+
+            self.optimizer.norm_reduce = reduce
+            return
+        raise ValueError(f"clip_grad with schedule {self.kind!r} on {self.mesh.pp} pipeline ranks: this rank holds "
+                         f"stages {self.local_stage_ids} of {self.P} and some stage lives on several ranks, so no sum "
+                         "over the pipeline group counts every stage exactly once")
 
     def _advance_rng(self):
         if self._uses_rng:  # one tiny launch per step, only for models with fused dropout
@@ -671,7 +711,7 @@ class PipelineEngine:
         # ... and when nothing else touches the gradients before the optimizer (one rank, no gradient
         # all-reduce, stepping this call), the last wave's reduction applies the optimizer step too
         fuse_step = (defer and train and step_optimizer and not self.grad_sync.enabled
-                     and hasattr(self.optimizer, "fused_args") and hasattr(s0, "grad_span")
+                     and self._sgd_fast and hasattr(s0, "grad_span")
                      and hasattr(s1, "grad_span"))
         step_fused = [False]
 
@@ -890,10 +930,10 @@ class PipelineEngine:
     def _small_step_ok(self, batch_size: int) -> bool:
         """Both stages of the 784-128-10 MLP on this (only) rank, fp32 weights, a batch the one-launch
         step kernel takes, and no gradients pending from an earlier step_optimizer=False call."""
-        if self._small_step is None:  # static: model shapes and placement only
+        if self._small_step is None:  # static: optimizer, model shapes and placement only
             s = self.stages
             self._small_step = bool(
-                self.device.type == "cuda" and self.mesh.world_size == 1 and self.P == 2 and 0 in s and 1 in s
+                self._sgd_fast and self.device.type == "cuda" and self.mesh.world_size == 1 and self.P == 2 and 0 in s and 1 in s
                 and self.optimizer.master is None and hasattr(s[0], "layers") and hasattr(s[1], "layers")
                 and [tuple(l.weight.shape) for l in s[0].layers()] == [(128, 784)]
                 and [tuple(l.weight.shape) for l in s[1].layers()] == [(10, 128)])
@@ -937,7 +977,7 @@ class PipelineEngine:
 
             s = self.stages
             self._cnn_step = bool(
-                self.device.type == "cuda" and self.mesh.world_size == 1 and self.P == 2 and 0 in s and 1 in s
+                self._sgd_fast and self.device.type == "cuda" and self.mesh.world_size == 1 and self.P == 2 and 0 in s and 1 in s
                 and isinstance(s[0], Network1Stage) and isinstance(s[1], Network2Stage)
                 and self.optimizer.master is None)
         # M == 1 only: the per-stage path draws one host dropout seed per micro-batch and stage, the
@@ -991,6 +1031,19 @@ class PipelineEngine:
             self.transport.all_reduce(v, group=group, async_op=False)
         v = v.cpu()
         return float(v[0]), int(v[1]), int(v[2])
+
+    def optimizer_metrics(self) -> Dict[str, float]:
+        """``lr`` (with a schedule or AdamW) and ``grad_norm`` (with clipping) of the last step, for the log.
+        Host-syncs: call it where the loss is read."""
+        opt, out = self.optimizer, {}
+        if self.optimizer_kind == "adamw":
+            if opt.steps:
+                out["lr"] = float(opt.last_lr)
+                if opt.last_grad_norm is not None:
+                    out["grad_norm"] = float(opt.last_grad_norm)
+        elif opt.schedule is not None:
+            out["lr"] = float(opt.lr)
+        return out
 
     def state_dicts(self) -> Dict[int, dict]:
         return {s: {k: v.detach().cpu().clone() for k, v in m.state_dict().items()} for s, m in self.stages.items()}

@@ -83,7 +83,11 @@ def run(args) -> dict:
         raise SystemExit(f"--dtype {args.dtype} is not supported for --model {args.model}")
     engine = PipelineEngine(spec, mesh, schedule_kind=args.schedule, num_microbatches=args.microbatches,
                             lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, seed=args.seed,
-                            debug_sync=args.debug_sync, timing=getattr(args, "timing", False))
+                            debug_sync=args.debug_sync, timing=getattr(args, "timing", False),
+                            optimizer=getattr(args, "optimizer", "sgd"),
+                            betas=(getattr(args, "beta1", 0.9), getattr(args, "beta2", 0.999)),
+                            eps=getattr(args, "eps", 1e-8), clip_grad=getattr(args, "clip_grad", 0.0),
+                            lr_schedule=cli.lr_schedule_of(args) if hasattr(args, "lr_schedule") else None)
     torch.manual_seed(args.seed * 7 + mesh.rank)  # dropout streams (reference: unseeded)
     if spec.input_kind == "tokens" and device.type == "cuda" and os.environ.get("SDML_GPT2_GEMM") == "lib":
         from .utils.tuned_gemm import use_tuned_gemms
@@ -149,6 +153,7 @@ def run(args) -> dict:
                     print(train_line(epoch, batch_idx, size, len(train_ds), nb, loss),
                           flush=True)
                     extra = {"timing_ms": engine.last_timing} if engine.timing else {}
+                    extra.update(engine.optimizer_metrics())
                     metrics.log(event="train", epoch=epoch, batch=batch_idx, loss=loss, samples_per_s=sps, **extra)
                 history["train"].append((epoch, batch_idx, loss))
         return last_idx

@@ -45,6 +45,9 @@ def main():
     ap.add_argument("--dtype", default=None, choices=[None, "fp32", "bf16"], help="resnet18: compute dtype")
     ap.add_argument("--pixels", default="auto", choices=["auto", "f32", "u8"],
                     help="image models: pixel storage (auto: uint8 for the MLPs at batches the uint8 kernels take)")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"])
+    ap.add_argument("--clip_grad", type=float, default=0.0, help="adamw: global gradient-norm clip (0: off)")
+    ap.add_argument("--weight_decay", type=float, default=0.0)
     a = ap.parse_args()
     kind, M, B, S = DEFAULTS[a.config]
     small = a.config in ("mlp", "ref_cnn") and (a.batch or B) <= 128
@@ -74,7 +77,9 @@ def main():
         # 107K vs 27.2K samples/s on one MI355X
         dt = torch.bfloat16
     spec = get_model_spec(a.config, stages, seq_len=S, **({"dtype": dt} if dt is not None else {}))
-    eng = PipelineEngine(spec, mesh, schedule_kind=kind, num_microbatches=M, lr=0.01, momentum=0.5, seed=1)
+    opt = {} if a.optimizer == "sgd" else {"optimizer": a.optimizer, "clip_grad": a.clip_grad}
+    eng = PipelineEngine(spec, mesh, schedule_kind=kind, num_microbatches=M, lr=0.01 if a.optimizer == "sgd" else 3e-4,
+                         momentum=0.5, weight_decay=a.weight_decay, seed=1, **opt)
     tuned = False
     if spec.input_kind == "tokens" and mesh.device.type == "cuda" and os.environ.get("SDML_GPT2_GEMM") == "lib":
         from simple_distributed_machine_learning_amd.utils.tuned_gemm import use_tuned_gemms
@@ -126,7 +131,8 @@ def main():
     if rank == 0:
         print(json.dumps({"config": a.config, "schedule": kind, "stages": stages, "ranks": world, "tp": a.tp,
                           "microbatches": M, "batch": GB, "seq_len": S, "dtype": str(spec.param_dtype), "graph": a.graph or False, "tuned_gemms": tuned,
-                          "pixels": a.pixels,
+                          "pixels": a.pixels, "optimizer": a.optimizer, "clip_grad": a.clip_grad,
+                          "weight_decay": a.weight_decay,
                           "value": round(GB * per_sample * a.steps / el, 1), "unit": unit,
                           "ms_per_step": round(el / a.steps * 1e3, 3), "loss": round(l / max(1, n), 4),
                           "bubble_model": round(eng.schedule(M, False).bubble_fraction(), 3)}))
