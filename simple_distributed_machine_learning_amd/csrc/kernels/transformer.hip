@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(CE_T) ce_fwd_bwd_kernel(const u16* __restrict_
       s = s * __expf(m - v) + 1.f;
       m = v;
       am = idx;
-    } else {
+    } else if (v != -INFINITY) {  // a -inf logit adds 0 (with m still -inf, v - m would be NaN)
       s += __expf(v - m);
     }
   };
@@ -92,7 +92,8 @@ __global__ void __launch_bounds__(CE_T) ce_fwd_bwd_kernel(const u16* __restrict_
       M = sm[i];
       AM = si[i];
     }
-  for (int i = 0; i < CE_T / 64; ++i) S += ss[i] * __expf(sm[i] - M);
+  for (int i = 0; i < CE_T / 64; ++i)
+    if (sm[i] != -INFINITY) S += ss[i] * __expf(sm[i] - M);  // a wave that saw only -inf adds 0
   const float lse = M + __logf(S);
   const int y = (int)tgt[row];
   const bool valid = y != ignore_index && y >= 0 && y < V;

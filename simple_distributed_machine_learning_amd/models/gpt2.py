@@ -147,14 +147,15 @@ class GPT2Stage(PipelineStage):
         if not train:
             with torch.no_grad():
                 logits = self(x)
-                l, c, n, _ = cross_entropy_sum(logits.reshape(-1, logits.shape[-1]), target.reshape(-1), 1.0, False)
+                l, c, n, _ = cross_entropy_sum(logits.reshape(-1, logits.shape[-1]), target.reshape(-1), 1.0, False,
+                                               ignore_index=None)
             return l, c, n
         if not self.is_first:
             x = x.detach().requires_grad_(True)
         with torch.enable_grad():
             logits = self(x)
         l, c, n, g = cross_entropy_sum(logits.detach().reshape(-1, logits.shape[-1]), target.reshape(-1),
-                                       loss_scale, True)
+                                       loss_scale, True, ignore_index=None)  # token targets: none ignored, no sync
         ctx["x"], ctx["logits"], ctx["glogits"] = x, logits, g.view_as(logits)
         return l, c, n
 

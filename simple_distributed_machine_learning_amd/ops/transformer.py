@@ -123,18 +123,25 @@ class LayerNorm(nn.LayerNorm):
         return layer_norm(x, self.weight, self.bias, self.eps)
 
 
-def cross_entropy_sum(logits, target, scale: float, need_grad: bool, ignore_index: int = -100):
+def cross_entropy_sum(logits, target, scale: float, need_grad: bool, ignore_index: int | None = -100):
     """Summed token cross-entropy on [rows, V] logits.
 
     Returns (loss_sum, correct, count, dlogits): dlogits = scale * d(loss_sum)/dlogits in the
     logits dtype (None unless ``need_grad``). bf16 on ROCm uses the fused single-row kernel
-    (never materialises fp32 logits)."""
+    (never materialises fp32 logits).
+
+    ``count`` is the number of rows whose target is not ``ignore_index``; counting them reads the device
+    (a host sync). ``ignore_index=None`` promises that no target is ignored: count is then the number of
+    rows and nothing is read back, which keeps a training step graph-capturable."""
+    no_ignore = ignore_index is None
+    if no_ignore:
+        ignore_index = -100
     if _hip_bf16(logits):
         if not (logits.stride(-1) == 1 and (logits.shape[0] <= 1 or logits.stride(0) >= logits.shape[1])):
             logits = logits.contiguous()  # (rows may be padded: the lm_head's [T, 50304]-strided logits stay in place)
         loss, ok, g = kernels().cross_entropy_bf16(logits, target.contiguous(), float(scale),
                                                    ignore_index, need_grad)
-        valid = int((target != ignore_index).sum()) if ignore_index >= 0 else target.numel()
+        valid = target.numel() if no_ignore else int((target != ignore_index).sum())
         return loss.sum(), ok.sum(), valid, g
     z = logits.float().detach().requires_grad_(need_grad)
     with torch.enable_grad():
@@ -145,8 +152,7 @@ def cross_entropy_sum(logits, target, scale: float, need_grad: bool, ignore_inde
         g = g.to(logits.dtype)
     valid = target != ignore_index
     correct = ((z.detach().argmax(1) == target) & valid).sum()
-    # no host sync unless an ignore_index can actually occur (keeps the step graph-capturable)
-    count = target.numel() if ignore_index < 0 else int(valid.sum())
+    count = target.numel() if no_ignore else int(valid.sum())
     return loss.detach(), correct, count, g
 
 
