@@ -88,6 +88,13 @@ def add_engine_args(parser: argparse.ArgumentParser):
     g.add_argument("--heartbeat", type=float, default=0.0, help="peer heartbeat timeout (s); 0 = off")
     g.add_argument("--dropout", type=float, default=0.5,
                    help="ref_cnn: Dropout2d / dropout probability (reference: 0.5; 0 makes a run deterministic)")
+    g.add_argument("--embd_pdrop", type=float, default=0.0,
+                   help="gpt2, gpt2_tiny: dropout on the token + position embedding (quantised to round(256 p) / 256)")
+    g.add_argument("--attn_pdrop", type=float, default=0.0,
+                   help="gpt2, gpt2_tiny: dropout on the attention probabilities, inside the flash kernels")
+    g.add_argument("--resid_pdrop", type=float, default=0.0,
+                   help="gpt2, gpt2_tiny: dropout on each block's attention / MLP output before the residual add "
+                        "(the three are refused with --schedule rotate and with other models)")
     g.add_argument("--eval_dropout", type=int, default=1,
                    help="ref_cnn: keep stage-1 dropout active in test() like the reference (1) or not (0)")
     g.add_argument("--ckpt_dir", default=None)

@@ -43,6 +43,7 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
+#include "dropout_hash.h"
 #include "kernels.h"
 
 namespace sdml {
@@ -164,7 +165,18 @@ struct AttnArgs {
   long sob, soh, sos;  // strides of o / dout
   float scale;         // softmax scale (1/sqrt(d))
   int causal;
+  DropArgs drop;       // attention-probability dropout (read by the DROP instantiations only)
 };
+
+// Attention dropout (DROP instantiations; dropout_hash.h). The mask word of (query q, keys 4 k4 .. 4 k4 + 3) is
+// drop_word(rkey, q, k4) with rkey = f(seed, counter, site, layer, sample0 + b, head0 + h), computed once per wave.
+// Forward and dQ: a lane owns a query and four consecutive accumulator registers are four consecutive keys, so one
+// word serves four scores. dK/dV: a lane owns a key and the registers run over queries: one word per score, of which
+// the lane uses byte (key & 3).
+__device__ __forceinline__ unsigned attn_drop_rkey(const DropArgs& d, int b, int hh) {
+  const unsigned long long skey = drop_site_key(drop_eff_seed(d.seed, d.ctr), d.site_layer);
+  return drop_row_key(skey, d.sample0 + (unsigned)b, d.head0 + (unsigned)hh);
+}
 
 // XCD-aware block order: the dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs, so
 // the blocks of one (batch, head) - which all read the same K/V (or Q/dO) tiles - would land on 8
@@ -178,7 +190,11 @@ __device__ __forceinline__ int xcd_block(int id, int n) { return (n % 8 == 0) ? 
 // feeds both sub-blocks' MFMAs and the wave carries two independent score -> softmax -> PV chains, so one sub-block's
 // exp / max / sum VALU work can issue beside the other's MFMAs. NWV waves per workgroup (4, or 2 with QS = 2: the
 // same 128 queries per workgroup, four workgroups per CU).
-template <int KBT, int QS, int NWV = NW, int MINW = 8 / NWV>  // keys per tile (64 or 128); MINW: waves per SIMD bound
+// DROP: dropout on the probabilities (compile-time: the DROP = false instantiations are the kernels without it). The
+// running max and the denominator l use the undropped p (LSE does not change); dropped p are zeroed before the bf16
+// pack; the 256 / (256 - T) factor multiplies the output once, together with 1 / l.
+// KBT: keys per tile (64 or 128); MINW: waves per SIMD bound
+template <int KBT, int QS, int NWV = NW, int MINW = 8 / NWV, bool DROP = false>
 __global__ void __launch_bounds__(64 * NWV, MINW) attn_fwd_kernel(AttnArgs a) {
   constexpr int NC = KBT / 32;  // 32-key sub-blocks per tile
   constexpr int QWV = QW * QS;  // queries per wave
@@ -211,6 +227,8 @@ __global__ void __launch_bounds__(64 * NWV, MINW) attn_fwd_kernel(AttnArgs a) {
     }
   }
   const float sl2 = a.scale * LOG2E;
+  unsigned rkey = 0;
+  if constexpr (DROP) rkey = attn_drop_rkey(a.drop, b, hh);
   float m[QS], l[QS];
   f32x16 o[QS][2];  // O^T[d][q]: d tile 0..1
 #pragma unroll
@@ -287,6 +305,18 @@ __global__ void __launch_bounds__(64 * NWV, MINW) attn_fwd_kernel(AttnArgs a) {
         rs += __shfl_xor(rs, 32);
         l[u] = l[u] * alpha[u] + rs;
         m[u] = mx;
+        if constexpr (DROP) {  // registers 4g..4g+3 are keys k0 + 32c + 8g + 4h + 0..3: one word per group
+          const unsigned qk = rkey ^ ((unsigned)qi[u] * 0x9E3779B1u);
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const unsigned wd = drop_fmix32(qk ^ ((unsigned)((k0 + 32 * c + 8 * g + 4 * h) >> 2) * 0x85EBCA77u));
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                s[u][c][4 * g + e] = drop_byte(wd, e) >= a.drop.T ? s[u][c][4 * g + e] : 0.f;
+            }
+        }
 #pragma unroll
         for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -317,7 +347,8 @@ __global__ void __launch_bounds__(64 * NWV, MINW) attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
     if (qi[u] >= a.S) continue;
-    const float inv = l[u] > 0.f ? 1.f / l[u] : 0.f;
+    float inv = l[u] > 0.f ? 1.f / l[u] : 0.f;
+    if constexpr (DROP) inv *= drop_scale(a.drop.T);
     u16* O = a.out + (long)b * a.sob + (long)hh * a.soh + (long)qi[u] * a.sos;
 #pragma unroll
     for (int d = 0; d < 2; ++d)
@@ -345,7 +376,9 @@ constexpr int BQ = 64;  // queries per iteration (backward)
 // NKT: 32-key tiles per wave (1: 128 keys per workgroup, 2 waves per SIMD; 2: 256 keys per workgroup, one wave per
 // SIMD with up to 512 registers: every Q / dO fragment read from LDS (rows and transposed) feeds both key tiles'
 // MFMAs, so the LDS reads per MFMA halve and each wave carries two independent accumulation chains)
-template <int NKT>
+// DROP: M regenerated from the hash. dV += dO^T (M o P), the 256 / (256 - T) factor applied once at the end;
+// dP_eff = M o dP * factor; dS = P (dP_eff - delta), delta = rowsum(dO * O) with the dropped O.
+template <int NKT, bool DROP = false>
 __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(AttnArgs a) {
   constexpr int KW = QW * NKT;  // keys per wave
   constexpr int KBW = KW * NW;  // keys per workgroup
@@ -378,6 +411,14 @@ __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(At
     }
   }
   const float sl2 = a.scale * LOG2E;
+  unsigned kkey[NKT];  // DROP: row key ^ this lane's key group term
+  float dsc = 1.f;
+  if constexpr (DROP) {
+    const unsigned rkey = attn_drop_rkey(a.drop, b, hh);
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) kkey[kt] = rkey ^ ((unsigned)(kj[kt] >> 2) * 0x85EBCA77u);
+    dsc = drop_scale(a.drop.T);
+  }
   f32x16 dv[NKT][2], dk[NKT][2];
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt)
@@ -445,8 +486,15 @@ __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(At
           for (int kt = 0; kt < NKT; ++kt) {
             float p = ex2(s[kt][i] * sl2 - lq);
             if (edge && kj[kt] > q0 + ql) p = 0.f;
-            s[kt][i] = p;
-            dp[kt][i] = p * (dp[kt][i] - dq);  // dS (scale applied to dK at the end)
+            if constexpr (DROP) {
+              const unsigned wd = drop_fmix32(kkey[kt] ^ ((unsigned)(q0 + ql) * 0x9E3779B1u));
+              const bool keep = drop_byte(wd, kj[kt] & 3) >= a.drop.T;
+              s[kt][i] = keep ? p : 0.f;
+              dp[kt][i] = p * ((keep ? dp[kt][i] * dsc : 0.f) - dq);
+            } else {
+              s[kt][i] = p;
+              dp[kt][i] = p * (dp[kt][i] - dq);  // dS (scale applied to dK at the end)
+            }
           }
         }
 #pragma unroll
@@ -479,7 +527,7 @@ __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(At
         u16x4 x, y;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          x[e] = f2bf(dv[kt][d][4 * g + e]);
+          x[e] = f2bf(DROP ? dv[kt][d][4 * g + e] * dsc : dv[kt][d][4 * g + e]);
           y[e] = f2bf(dk[kt][d][4 * g + e] * a.scale);
         }
         *reinterpret_cast<u16x4*>(DV + 32 * d + 8 * g + 4 * h) = x;
@@ -494,6 +542,8 @@ __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(At
 //   dP^T = V dO^T    (A = V rows, B = dO rows of this wave -> registers)
 //   dS^T = P^T (dP^T - delta[q])
 //   dQ^T[d][q] += K^T[d][k] dS^T[k][q]   (A = K^T by transposed reads, B = dS^T registers)
+// DROP: dS^T = P^T (M o dP^T * 256 / (256 - T) - delta[q]), M regenerated from the hash (one word per four keys)
+template <bool DROP = false>
 __global__ void __launch_bounds__(256, 2) attn_bwd_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) u16 Ks[2][TR * HD];
   __shared__ __attribute__((aligned(16))) u16 Vs[2][TR * HD];
@@ -533,6 +583,12 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_kernel(AttnArgs a) {
   dl += __shfl_xor(dl, 32);
   if (h == 0 && qi < a.S) a.delta[(long)bh * a.S + qi] = dl;
   const float sl2 = a.scale * LOG2E;
+  unsigned qk = 0;
+  float dsc = 1.f;
+  if constexpr (DROP) {
+    qk = attn_drop_rkey(a.drop, b, hh) ^ ((unsigned)qi * 0x9E3779B1u);
+    dsc = drop_scale(a.drop.T);
+  }
   f32x16 dq[2] = {zero16(), zero16()};
   const int kend = a.causal ? min(a.S, qb * QB + QB) : a.S;
   TileRegs<TR> kr, vr;
@@ -567,7 +623,22 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_kernel(AttnArgs a) {
         for (int i = 0; i < 16; ++i) {
           float p = ex2(s[i] * sl2 - lse);
           p = ((i & 3) + 8 * (i >> 2) > lim) ? 0.f : p;
-          dp[i] = p * (dp[i] - dl);
+          if constexpr (DROP) {
+            s[i] = p;
+          } else {
+            dp[i] = p * (dp[i] - dl);
+          }
+        }
+        if constexpr (DROP) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const unsigned wd = drop_fmix32(qk ^ ((unsigned)((k0 + 32 * c + 8 * g + 4 * h) >> 2) * 0x85EBCA77u));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int i = 4 * g + e;
+              dp[i] = s[i] * ((drop_byte(wd, e) >= a.drop.T ? dp[i] * dsc : 0.f) - dl);
+            }
+          }
         }
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
@@ -620,6 +691,7 @@ AttnArgs make_args(const AttnShape& s) {
   a.sos = s.sos;
   a.scale = s.scale;
   a.causal = s.causal;
+  a.drop = s.drop;
   return a;
 }
 
@@ -630,6 +702,12 @@ void attention_set_fwd_kb(int kb) { g_fwd_kb = kb; }
 
 void attention_fwd_bf16(const AttnShape& s, hipStream_t stream) {
   AttnArgs a = make_args(s);
+  if (s.drop.T) {  // dropout: the default tile shape with the mask compiled in (ATTN_FWD_QS, ATTN_OCC and
+                   // attention_set_fwd_kb choose among the kernels without dropout only)
+    const int nqb = (s.S + QB - 1) / QB;
+    hipLaunchKernelGGL((attn_fwd_kernel<64, 1, NW, 8 / NW, true>), dim3(nqb * s.B * s.H), dim3(256), 0, stream, a);
+    return;
+  }
   const int qs = knob(KNOB_ATTN_FWD_QS);
   if (qs == 2) {  // 64 queries per wave (two sub-blocks), 4 waves: 256 per workgroup
     const int nqb = (s.S + 2 * QB - 1) / (2 * QB);
@@ -657,7 +735,15 @@ void attention_bwd_bf16(const AttnShape& s, hipStream_t stream) {
   AttnArgs a = make_args(s);
   const int nb = (s.S + QB - 1) / QB;
   // dQ first: it computes delta = rowsum(dO * O) for its own queries and writes it for dK/dV
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(nb * s.B * s.H), dim3(256), 0, stream, a);
+  const bool run_dq = s.bwd_parts & 1, run_dkdv = s.bwd_parts & 2;
+  if (s.drop.T) {  // dropout: the default shapes with the mask compiled in (the knobs below do not apply)
+    if (run_dq) hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, dim3(nb * s.B * s.H), dim3(256), 0, stream, a);
+    if (run_dkdv)
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<1, true>), dim3(nb * s.B * s.H), dim3(256), 0, stream, a);
+    return;
+  }
+  if (run_dq) hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3(nb * s.B * s.H), dim3(256), 0, stream, a);
+  if (!run_dkdv) return;
   // dK/dV: 128 keys per workgroup (one 32-key tile per wave); knob ATTN_DKDV_KT = 2: 256 (measured slower)
   if (knob(KNOB_ATTN_DKDV_KT) == 2) {
     const int nk2 = (s.S + 2 * QB - 1) / (2 * QB);

@@ -51,11 +51,21 @@ __global__ void __launch_bounds__(256) gelu_bwd_kernel(const u16x8* __restrict__
 }
 
 // one wave per token row: 4 bf16 (8 B) per lane per step
+// DROP (compile-time): embedding dropout, out = bf16((wte + wpe) * M * 256 / (256 - T)) with one rounding; row r is
+// position r % S of sample drop.sample0 + r / S, one mask word (dropout_hash.h) per four channels
+template <bool DROP>
 __global__ void __launch_bounds__(256) embed_fwd_kernel(const int64_t* __restrict__ tok, const u16* __restrict__ wte,
                                                         const u16* __restrict__ wpe, u16* __restrict__ out, int rows,
-                                                        int S, int C, int V) {
+                                                        int S, int C, int V, DropArgs drop) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
+  unsigned pk = 0;
+  float dsc = 1.f;
+  if constexpr (DROP) {
+    const unsigned long long skey = drop_site_key(drop_eff_seed(drop.seed, drop.ctr), drop.site_layer);
+    pk = drop_row_key(skey, drop.sample0 + (unsigned)(row / S), 0) ^ ((unsigned)(row % S) * 0x9E3779B1u);
+    dsc = drop_scale(drop.T);
+  }
   int64_t t = tok[row];
   t = t < 0 ? 0 : (t >= V ? V - 1 : t);  // (host validates the range in debug mode)
   const u16x4* a = reinterpret_cast<const u16x4*>(wte + t * C);
@@ -64,9 +74,43 @@ __global__ void __launch_bounds__(256) embed_fwd_kernel(const int64_t* __restric
   for (int c = lane; c < C / 4; c += 64) {
     const u16x4 va = a[c], vp = p[c];
     u16x4 r;
+    if constexpr (DROP) {
+      const unsigned wd = drop_fmix32(pk ^ ((unsigned)c * 0x85EBCA77u));
 #pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = f2bf(bf2f(va[e]) + bf2f(vp[e]));
+      for (int e = 0; e < 4; ++e)
+        r[e] = f2bf(drop_byte(wd, e) >= drop.T ? (bf2f(va[e]) + bf2f(vp[e])) * dsc : 0.f);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) r[e] = f2bf(bf2f(va[e]) + bf2f(vp[e]));
+    }
     o[c] = r;
+  }
+}
+
+// Residual dropout outside a LayerNorm (the bare x + m that ends a non-final stage) and the masked scale that is its
+// backward (and the embedding dropout's): out = bf16(x + M o h * 256 / (256 - T)), x == nullptr: out = bf16(M o h * f).
+// One thread per four channels (one mask word); rows of C channels, row r = position r % S of sample sample0 + r / S.
+__global__ void __launch_bounds__(256) dropout_add_kernel(const u16* __restrict__ x, const u16* __restrict__ h,
+                                                          u16* __restrict__ out, int64_t rows, int S, int C,
+                                                          DropArgs drop) {
+  const int c4 = C / 4;
+  const int64_t n = rows * c4;
+  const unsigned long long skey = drop_site_key(drop_eff_seed(drop.seed, drop.ctr), drop.site_layer);
+  const float dsc = drop_scale(drop.T);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / c4;
+    const int c = (int)(i - row * c4);
+    const unsigned rk = drop_row_key(skey, drop.sample0 + (unsigned)(row / S), 0);
+    const unsigned wd = drop_word(rk, (unsigned)(row % S), (unsigned)c);
+    const u16x4 hv = *reinterpret_cast<const u16x4*>(h + i * 4);
+    u16x4 xv = {0, 0, 0, 0}, r;
+    if (x) xv = *reinterpret_cast<const u16x4*>(x + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = drop_byte(wd, e) >= drop.T ? bf2f(hv[e]) * dsc : 0.f;
+      r[e] = f2bf(x ? bf2f(xv[e]) + d : d);
+    }
+    *reinterpret_cast<u16x4*>(out + i * 4) = r;
   }
 }
 
@@ -182,9 +226,27 @@ void gelu_bwd_bf16(const void* gy, const void* x, void* gx, int64_t n, hipStream
 void embedding_fwd_bf16(const int64_t* tok, const void* wte, const void* wpe, void* out, int rows, int S, int C, int V,
                         hipStream_t stream) {
   if (C % 4 || rows <= 0) return;
-  hipLaunchKernelGGL(embed_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, tok,
+  hipLaunchKernelGGL(embed_fwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, stream, tok,
                      reinterpret_cast<const u16*>(wte), reinterpret_cast<const u16*>(wpe), reinterpret_cast<u16*>(out),
-                     rows, S, C, V);
+                     rows, S, C, V, DropArgs{});
+}
+
+void embedding_drop_fwd_bf16(const int64_t* tok, const void* wte, const void* wpe, void* out, int rows, int S, int C,
+                             int V, const DropArgs& drop, hipStream_t stream) {
+  if (C % 4 || rows <= 0) return;
+  if (!drop.T) abort();  // host contract
+  hipLaunchKernelGGL(embed_fwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, stream, tok,
+                     reinterpret_cast<const u16*>(wte), reinterpret_cast<const u16*>(wpe), reinterpret_cast<u16*>(out),
+                     rows, S, C, V, drop);
+}
+
+void dropout_add_bf16(const void* x, const void* h, void* out, int64_t rows, int S, int C, const DropArgs& drop,
+                      hipStream_t stream) {
+  if (rows <= 0) return;
+  if (C % 4 || !drop.T || S <= 0) abort();  // host contract
+  hipLaunchKernelGGL(dropout_add_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, stream,
+                     reinterpret_cast<const u16*>(x), reinterpret_cast<const u16*>(h), reinterpret_cast<u16*>(out),
+                     rows, S, C, drop);
 }
 
 void embedding_bwd_bf16(const void* g, const int64_t* sorted_tok, const int64_t* perm, void* gwte, void* gwpe, int B,

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "dropout_hash.h"
 #include "knobs.h"
 
 namespace sdml {
@@ -297,6 +298,15 @@ void layernorm_bwd_bf16(const void* x, const void* w, const void* gy, const floa
 void layernorm_bwd_bf16_accum(const void* x, const void* w, const void* gy, const float* mean, const float* rstd,
                               void* dx, float* workspace, void* gw, void* gb, int rows, int D, hipStream_t stream,
                               const void* gadd = nullptr);
+// Residual dropout (dropout_hash.h; drop.T > 0) fused into the add + LayerNorm: xs = bf16(x + M o h * 256 / (256 - T)),
+// y = LN(xs); row r is position r % S of sample drop.sample0 + r / S. Its backward writes dx (both addends' d) and
+// dh = bf16(d * M * 256 / (256 - T)), rounded from the fp32 d.
+void add_layernorm_drop_fwd_bf16(const void* x, const void* h, const void* w, const void* b, void* xs, void* y,
+                                 float* mean, float* rstd, int rows, int D, int S, float eps, const DropArgs& drop,
+                                 hipStream_t stream);
+void layernorm_bwd_bf16_accum_drop(const void* x, const void* w, const void* gy, const float* mean, const float* rstd,
+                                   void* dx, void* dh, float* workspace, void* gw, void* gb, int rows, int D, int S,
+                                   const void* gadd, const DropArgs& drop, hipStream_t stream);
 // bias gradient of a bf16 linear layer: gb[n] (bf16) += sum_m gy[m][n]; workspace fp32
 // [bias_grad_blocks(M) * N]. Deterministic (fixed-order partial sums).
 int bias_grad_blocks(int M);
@@ -322,6 +332,13 @@ void gelu_bwd_bf16(const void* gy, const void* x, void* gx, int64_t n, hipStream
 // out[r] = wte[tok[r]] + wpe[r % S]  (rows = B * S, C % 4 == 0)
 void embedding_fwd_bf16(const int64_t* tok, const void* wte, const void* wpe, void* out, int rows, int S, int C, int V,
                         hipStream_t stream);
+// the same with embedding dropout: out[r] = bf16((wte[tok[r]] + wpe[r % S]) * M * 256 / (256 - T))  (drop.T > 0)
+void embedding_drop_fwd_bf16(const int64_t* tok, const void* wte, const void* wpe, void* out, int rows, int S, int C,
+                             int V, const DropArgs& drop, hipStream_t stream);
+// out = bf16(x + M o h * 256 / (256 - T)) over rows of C channels (C % 4 == 0, drop.T > 0); x == nullptr: the masked
+// scale alone (the backward of this add's h and of the embedding dropout)
+void dropout_add_bf16(const void* x, const void* h, void* out, int64_t rows, int S, int C, const DropArgs& drop,
+                      hipStream_t stream);
 // gwpe[s] += sum_b g[b][s]; gwte[v] += sum over positions of token v (sorted_tok / perm: the tokens sorted
 // stably, with their positions) - deterministic, either gradient may be null
 void embedding_bwd_bf16(const void* g, const int64_t* sorted_tok, const int64_t* perm, void* gwte, void* gwpe, int B,
@@ -468,6 +485,9 @@ struct AttnShape {
   long sqb = 0, sqh = 0, sqs = 0, sob = 0, soh = 0, sos = 0;
   float scale = 1.f;
   int causal = 1;
+  DropArgs drop;  // dropout on the attention probabilities (dropout_hash.h); drop.T == 0: off, the plain kernels
+                  // (drop.T > 0 runs the default tile shapes: the attention knobs and attention_set_fwd_kb do not apply)
+  int bwd_parts = 3;  // backward kernels to launch: 1 dQ (writes delta), 2 dK/dV (reads delta), 3 both (timing tools)
 };
 void attention_fwd_bf16(const AttnShape& s, hipStream_t stream);
 void attention_set_fwd_kb(int kb);  // tuning: keys per forward tile (0 = default, 64, 128)

@@ -49,6 +49,9 @@ enum KnobId : int {
   KNOB_GEMM_BF16_TR,         // 1 (default): bf16 NT GEMM (4-phase) accumulates C^T: 8-byte row pieces in the epilogue
   KNOB_WGRAD_NFAST,          // bf16 weight gradient tile order: -1 auto (N fastest when gy is larger than the MALL), 0, 1
   KNOB_ATTN_DKDV_KT,         // attention dK/dV: 32-key tiles per wave (1: 2 waves per SIMD, 2: 1 wave per SIMD)
+                             // (the attention knobs ATTN_DKDV_KT, ATTN_FWD_QS, ATTN_OCC and attention_set_fwd_kb pick
+                             // among the kernels WITHOUT dropout; a call with attention dropout always runs the default
+                             // shapes, 64-key tiles, 32 queries / 32 keys per wave, 2 waves per SIMD, and ignores them)
   KNOB_U8_FH_ROWS512,        // fused uint8 forward + head: 512-row blocks (two head passes): 0 (default, measured no
                              // faster: profiles/r6_fused_rows512_ab.jsonl), 1, -1 auto (when they cover every CU)
   KNOB_GEMM_GROUP_M,         // bf16 / fp16-plane GEMM tile order: 0 M fastest, g > 0 groups of g m-tiles (tile_order.h)

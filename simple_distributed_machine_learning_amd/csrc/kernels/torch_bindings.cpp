@@ -1769,10 +1769,37 @@ void bias_grad_bf16_(torch::Tensor gy, torch::Tensor gb) {
                        cur_stream());
 }
 
+// Dropout on the attention probabilities (dropout_hash.h): threshold T = round(256 p) (0: off), the run's seed, the
+// device step counter (int64 [1], optional), site << 16 | global layer, the dataset index of batch row 0 and the
+// global index of head 0.
+sdml::DropArgs attn_drop_args(const torch::Tensor& q, int64_t drop_t, int64_t drop_seed,
+                              const c10::optional<torch::Tensor>& drop_ctr, int64_t drop_site_layer, int64_t sample0,
+                              int64_t head0) {
+  sdml::DropArgs d;
+  TORCH_CHECK(drop_t >= 0 && drop_t <= 255, "attention: drop_t must be in [0, 255] (round(256 p))");
+  if (drop_t == 0) return d;
+  TORCH_CHECK(sample0 >= 0 && head0 >= 0 && sample0 + q.size(0) <= 0xFFFFFFFFll && head0 + q.size(2) <= 0xFFFFFFFFll,
+              "attention: sample0 / head0 out of range");
+  d.T = (unsigned)drop_t;
+  d.seed = (unsigned long long)drop_seed;
+  d.site_layer = (unsigned)drop_site_layer;
+  d.sample0 = (unsigned)sample0;
+  d.head0 = (unsigned)head0;
+  if (drop_ctr.has_value()) {
+    const auto& c = *drop_ctr;
+    TORCH_CHECK(c.is_cuda() && c.scalar_type() == torch::kInt64 && c.numel() == 1 && c.device() == q.device(),
+                "attention: drop_ctr must be one int64 on the tensors' device");
+    d.ctr = reinterpret_cast<const long long*>(c.data_ptr<int64_t>());
+  }
+  return d;
+}
+
 // q, k, v: [B, S, H, 64] bf16 views sharing strides (d contiguous), e.g. slices of the fused
 // qkv projection. Returns (out [B, S, H, 64] contiguous, lse fp32 [B*H*S]).
 std::tuple<torch::Tensor, torch::Tensor> attention_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale,
-                                                       bool causal) {
+                                                       bool causal, int64_t drop_t, int64_t drop_seed,
+                                                       c10::optional<torch::Tensor> drop_ctr, int64_t drop_site_layer,
+                                                       int64_t sample0, int64_t head0) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16, "attention: bf16 device tensors");
   TORCH_CHECK(q.dim() == 4 && q.size(3) == 64 && q.stride(3) == 1, "attention: [B, S, H, 64] with contiguous d");
   TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes() && k.strides() == q.strides() &&
@@ -1802,19 +1829,35 @@ std::tuple<torch::Tensor, torch::Tensor> attention_fwd(torch::Tensor q, torch::T
   a.soh = out.stride(2);
   a.scale = (float)scale;
   a.causal = causal ? 1 : 0;
+  a.drop = attn_drop_args(q, drop_t, drop_seed, drop_ctr, drop_site_layer, sample0, head0);
   sdml::attention_fwd_bf16(a, cur_stream());
   return {out, lse};
 }
 
 // grads written into dqkv (same strides as q/k/v views of it: pass dq, dk, dv views)
 void attention_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor out, torch::Tensor dout,
-                   torch::Tensor lse, torch::Tensor dq, torch::Tensor dk, torch::Tensor dv, double scale, bool causal) {
+                   torch::Tensor lse, torch::Tensor dq, torch::Tensor dk, torch::Tensor dv, double scale, bool causal,
+                   int64_t drop_t, int64_t drop_seed, c10::optional<torch::Tensor> drop_ctr, int64_t drop_site_layer,
+                   int64_t sample0, int64_t head0, int64_t parts, c10::optional<torch::Tensor> delta_buf) {
   TORCH_CHECK(out.is_contiguous() && dout.is_contiguous() && out.sizes() == dout.sizes(), "attention bwd: out/dout");
   TORCH_CHECK(dq.strides() == q.strides() && dk.strides() == q.strides() && dv.strides() == q.strides(),
               "attention bwd: grads must use the q/k/v strides");
   const int64_t B = q.size(0), S = q.size(1), H = q.size(2);
-  auto delta = torch::empty({B * H * S}, q.options().dtype(torch::kFloat32));
+  // parts / delta (timing tools): the dQ kernel (1) writes delta = rowsum(dO * O), the dK/dV kernel (2) reads it; a
+  // call that runs only one of them shares delta with the other through the caller's buffer
+  TORCH_CHECK(parts >= 1 && parts <= 3, "attention bwd: parts must be 1 (dQ), 2 (dK/dV) or 3 (both)");
+  TORCH_CHECK(parts == 3 || delta_buf.has_value(), "attention bwd: a partial backward needs a delta buffer");
+  torch::Tensor delta;
+  if (delta_buf.has_value()) {
+    delta = *delta_buf;
+    TORCH_CHECK(delta.is_cuda() && delta.scalar_type() == torch::kFloat32 && delta.is_contiguous() &&
+                    delta.numel() == B * H * S && delta.device() == q.device(),
+                "attention bwd: delta must be a contiguous fp32 [B * H * S] tensor on the device");
+  } else {
+    delta = torch::empty({B * H * S}, q.options().dtype(torch::kFloat32));
+  }
   sdml::AttnShape a;
+  a.bwd_parts = (int)parts;
   a.q = q.data_ptr();
   a.k = k.data_ptr();
   a.v = v.data_ptr();
@@ -1836,7 +1879,107 @@ void attention_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Ten
   a.soh = out.stride(2);
   a.scale = (float)scale;
   a.causal = causal ? 1 : 0;
+  a.drop = attn_drop_args(q, drop_t, drop_seed, drop_ctr, drop_site_layer, sample0, head0);
   sdml::attention_bwd_bf16(a, cur_stream());
+}
+
+// ---- GPT-2 dropout at the element-wise sites (dropout_hash.h). x: [B, S, C] (row r of the flattened tensor is
+// position r % S of sample sample0 + r / S); drop_t = round(256 p) in 1..255.
+sdml::DropArgs site_drop_args(const torch::Tensor& x, int64_t drop_t, int64_t drop_seed,
+                              const c10::optional<torch::Tensor>& drop_ctr, int64_t drop_site_layer, int64_t sample0) {
+  TORCH_CHECK(drop_t >= 1 && drop_t <= 255, "dropout: drop_t must be in [1, 255] (round(256 p))");
+  TORCH_CHECK(x.dim() == 3, "dropout: [B, S, C] tensors");
+  return attn_drop_args(x, drop_t, drop_seed, drop_ctr, drop_site_layer, sample0, 0);
+}
+
+// xs = bf16(x + drop(h)), y = LN(xs); returns (xs, y, mean, rstd)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> add_layernorm_drop_fwd_bf16(
+    torch::Tensor x, torch::Tensor h, torch::Tensor w, torch::Tensor b, double eps, int64_t drop_t, int64_t drop_seed,
+    c10::optional<torch::Tensor> drop_ctr, int64_t drop_site_layer, int64_t sample0) {
+  check_bf16_cuda(x, "x");
+  check_bf16_cuda(h, "h");
+  check_bf16_cuda(w, "w");
+  check_bf16_cuda(b, "b");
+  TORCH_CHECK(x.sizes() == h.sizes(), "add_layernorm: x / h shape mismatch");
+  const auto drop = site_drop_args(x, drop_t, drop_seed, drop_ctr, drop_site_layer, sample0);
+  const int64_t D = x.size(-1), rows = x.numel() / D;
+  TORCH_CHECK(D % 8 == 0 && D <= 4096 && w.numel() == D && b.numel() == D, "layernorm: D % 8 == 0, D <= 4096");
+  auto xs = torch::empty_like(x);
+  auto y = torch::empty_like(x);
+  auto f = x.options().dtype(torch::kFloat32);
+  auto mean = torch::empty({rows}, f), rstd = torch::empty({rows}, f);
+  sdml::add_layernorm_drop_fwd_bf16(x.data_ptr(), h.data_ptr(), w.data_ptr(), b.data_ptr(), xs.data_ptr(),
+                                    y.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(), (int)rows, (int)D,
+                                    (int)x.size(1), (float)eps, drop, cur_stream());
+  return {xs, y, mean, rstd};
+}
+
+// LayerNorm backward of the fused add + LayerNorm with residual dropout; returns (dx, dh)
+std::tuple<torch::Tensor, torch::Tensor> layernorm_bwd_bf16_accum_drop(
+    torch::Tensor x, torch::Tensor w, torch::Tensor gy, torch::Tensor mean, torch::Tensor rstd, torch::Tensor gw,
+    torch::Tensor gb, c10::optional<torch::Tensor> gadd, int64_t drop_t, int64_t drop_seed,
+    c10::optional<torch::Tensor> drop_ctr, int64_t drop_site_layer, int64_t sample0) {
+  check_bf16_cuda(x, "x");
+  check_bf16_cuda(w, "w");
+  check_bf16_cuda(gy, "gy");
+  check_bf16_cuda(gw, "gw");
+  check_bf16_cuda(gb, "gb");
+  check_f32_cuda(mean, "mean");
+  check_f32_cuda(rstd, "rstd");
+  const auto drop = site_drop_args(x, drop_t, drop_seed, drop_ctr, drop_site_layer, sample0);
+  const int64_t D = x.size(-1), rows = x.numel() / D;
+  TORCH_CHECK(D % 8 == 0 && D <= 4096 && gy.sizes() == x.sizes() && mean.numel() == rows && rstd.numel() == rows &&
+                  w.numel() == D && gw.numel() == D && gb.numel() == D,
+              "ln bwd shapes");
+  const void* ga = nullptr;
+  if (gadd.has_value() && gadd->defined()) {
+    check_bf16_cuda(*gadd, "gadd");
+    TORCH_CHECK(gadd->sizes() == x.sizes() && gadd->is_contiguous(), "ln bwd: gadd must match x (contiguous)");
+    ga = gadd->data_ptr();
+  }
+  auto dx = torch::empty_like(x);
+  auto dh = torch::empty_like(x);
+  auto ws = torch::empty({(int64_t)sdml::layernorm_bwd_blocks(rows) * 2 * D}, x.options().dtype(torch::kFloat32));
+  sdml::layernorm_bwd_bf16_accum_drop(x.data_ptr(), w.data_ptr(), gy.data_ptr(), mean.data_ptr<float>(),
+                                      rstd.data_ptr<float>(), dx.data_ptr(), dh.data_ptr(), ws.data_ptr<float>(),
+                                      gw.data_ptr(), gb.data_ptr(), (int)rows, (int)D, (int)x.size(1), ga, drop,
+                                      cur_stream());
+  return {dx, dh};
+}
+
+// out = bf16(x + drop(h)); x = None: out = bf16(drop(h)) (the masked scale: the backward of h, and of the embedding
+// dropout)
+torch::Tensor dropout_add_bf16(c10::optional<torch::Tensor> x, torch::Tensor h, int64_t drop_t, int64_t drop_seed,
+                               c10::optional<torch::Tensor> drop_ctr, int64_t drop_site_layer, int64_t sample0) {
+  check_bf16_cuda(h, "h");
+  const auto drop = site_drop_args(h, drop_t, drop_seed, drop_ctr, drop_site_layer, sample0);
+  const int64_t C = h.size(-1), rows = h.numel() / C;
+  TORCH_CHECK(C % 4 == 0, "dropout_add: C % 4 == 0");
+  const void* px = nullptr;
+  if (x.has_value() && x->defined()) {
+    check_bf16_cuda(*x, "x");
+    TORCH_CHECK(x->sizes() == h.sizes(), "dropout_add: x / h shape mismatch");
+    px = x->data_ptr();
+  }
+  auto out = torch::empty_like(h);
+  sdml::dropout_add_bf16(px, h.data_ptr(), out.data_ptr(), rows, (int)h.size(1), (int)C, drop, cur_stream());
+  return out;
+}
+
+torch::Tensor embedding_drop_fwd_bf16(torch::Tensor tok, torch::Tensor wte, torch::Tensor wpe, int64_t drop_t,
+                                      int64_t drop_seed, c10::optional<torch::Tensor> drop_ctr,
+                                      int64_t drop_site_layer, int64_t sample0) {
+  TORCH_CHECK(tok.is_cuda() && tok.scalar_type() == torch::kInt64 && tok.is_contiguous() && tok.dim() == 2,
+              "embedding: tokens must be a contiguous int64 [B, S] device tensor");
+  check_bf16_cuda(wte, "wte");
+  check_bf16_cuda(wpe, "wpe");
+  const int64_t B = tok.size(0), S = tok.size(1), C = wte.size(1);
+  TORCH_CHECK(wpe.size(1) == C && wpe.size(0) >= S && C % 4 == 0, "embedding: shape mismatch");
+  auto out = torch::empty({B, S, C}, wte.options());
+  const auto drop = site_drop_args(out, drop_t, drop_seed, drop_ctr, drop_site_layer, sample0);
+  sdml::embedding_drop_fwd_bf16(tok.data_ptr<int64_t>(), wte.data_ptr(), wpe.data_ptr(), out.data_ptr(), (int)(B * S),
+                                (int)S, (int)C, (int)wte.size(0), drop, cur_stream());
+  return out;
 }
 
 
@@ -2072,8 +2215,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gadd") = py::none());
   m.def("add_layernorm_fwd_bf16", &add_layernorm_fwd_bf16, "fused residual add + LayerNorm forward (bf16)");
   m.def("bias_grad_bf16_", &bias_grad_bf16_, "gb += column sums of gy (bf16, deterministic)");
-  m.def("attention_fwd", &attention_fwd, "causal flash attention forward (bf16, d=64)");
-  m.def("attention_bwd", &attention_bwd, "causal flash attention backward (bf16, d=64)");
+  m.def("attention_fwd", &attention_fwd, "causal flash attention forward (bf16, d=64)", py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("scale"), py::arg("causal"), py::arg("drop_t") = 0, py::arg("drop_seed") = 0,
+        py::arg("drop_ctr") = py::none(), py::arg("drop_site_layer") = 0, py::arg("sample0") = 0,
+        py::arg("head0") = 0);
+  m.def("attention_bwd", &attention_bwd, "causal flash attention backward (bf16, d=64)", py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
+        py::arg("scale"), py::arg("causal"), py::arg("drop_t") = 0, py::arg("drop_seed") = 0,
+        py::arg("drop_ctr") = py::none(), py::arg("drop_site_layer") = 0, py::arg("sample0") = 0,
+        py::arg("head0") = 0, py::arg("parts") = 3, py::arg("delta") = py::none());
+  m.def("add_layernorm_drop_fwd_bf16", &add_layernorm_drop_fwd_bf16,
+        "fused residual dropout + add + LayerNorm forward (bf16)", py::arg("x"), py::arg("h"), py::arg("w"),
+        py::arg("b"), py::arg("eps"), py::arg("drop_t"), py::arg("drop_seed"), py::arg("drop_ctr") = py::none(),
+        py::arg("drop_site_layer") = 0, py::arg("sample0") = 0);
+  m.def("layernorm_bwd_bf16_accum_drop", &layernorm_bwd_bf16_accum_drop,
+        "LayerNorm backward of the fused residual dropout + add + LayerNorm: (dx, dh)", py::arg("x"), py::arg("w"),
+        py::arg("gy"), py::arg("mean"), py::arg("rstd"), py::arg("gw"), py::arg("gb"), py::arg("gadd"),
+        py::arg("drop_t"), py::arg("drop_seed"), py::arg("drop_ctr") = py::none(), py::arg("drop_site_layer") = 0,
+        py::arg("sample0") = 0);
+  m.def("dropout_add_bf16", &dropout_add_bf16, "x + dropout(h) (x = None: dropout(h)), bf16", py::arg("x"),
+        py::arg("h"), py::arg("drop_t"), py::arg("drop_seed"), py::arg("drop_ctr") = py::none(),
+        py::arg("drop_site_layer") = 0, py::arg("sample0") = 0);
+  m.def("embedding_drop_fwd_bf16", &embedding_drop_fwd_bf16, "token + position embedding with dropout (bf16)",
+        py::arg("tok"), py::arg("wte"), py::arg("wpe"), py::arg("drop_t"), py::arg("drop_seed"),
+        py::arg("drop_ctr") = py::none(), py::arg("drop_site_layer") = 0, py::arg("sample0") = 0);
   m.def("attention_set_fwd_kb", &sdml::attention_set_fwd_kb, "attention forward keys per tile (tuning)");
   m.def("gemm_f32x3", &gemm_f32x3_op, "fp32 GEMM via the bf16x3 split on bf16 MFMA", py::arg("A"), py::arg("B"),
         py::arg("C"), py::arg("a_kmajor"), py::arg("b_kmajor"), py::arg("epi") = 0, py::arg("bias") = py::none(),

@@ -240,14 +240,22 @@ constexpr int LN_T = 256;
 
 // res != nullptr: the row is first the residual sum xs = bf16(x + res) (stored to xs, exactly the
 // unfused bf16 add), and the statistics are those of xs — one pass instead of add + LayerNorm
-template <int LN_MAXV>
+// DROP (compile-time; needs res): residual dropout, xs = bf16(x + M o res * 256 / (256 - T)), still one rounding. Row
+// r is position r % S of sample drop.sample0 + r / S; one mask word per four channels (dropout_hash.h).
+template <int LN_MAXV, bool DROP = false>
 __global__ void __launch_bounds__(LN_T) ln_fwd_kernel(const u16* __restrict__ x, const u16* __restrict__ res,
                                                       const u16* __restrict__ w, const u16* __restrict__ b,
                                                       u16* __restrict__ xs, u16* __restrict__ y,
                                                       float* __restrict__ mean, float* __restrict__ rstd, int rows,
-                                                      int D, float eps) {
+                                                      int D, float eps, DropArgs drop, int S) {
   const int lane = threadIdx.x & 63;
   const int nch = D / 8;
+  unsigned long long skey = 0;
+  float dsc = 1.f;
+  if constexpr (DROP) {
+    skey = drop_site_key(drop_eff_seed(drop.seed, drop.ctr), drop.site_layer);
+    dsc = drop_scale(drop.T);
+  }
   // this lane's gamma / beta chunks, once (they were re-read for every row)
   u16x8 wv[LN_MAXV], bv[LN_MAXV];
 #pragma unroll
@@ -260,12 +268,27 @@ __global__ void __launch_bounds__(LN_T) ln_fwd_kernel(const u16* __restrict__ x,
     const u16* xr = x + (size_t)row * D;
     u16x8 v[LN_MAXV];
     float sum = 0.f;
+    unsigned pk = 0;  // DROP: row key ^ position term
+    if constexpr (DROP)
+      pk = drop_row_key(skey, drop.sample0 + (unsigned)(row / S), 0) ^ ((unsigned)(row % S) * 0x9E3779B1u);
 #pragma unroll
     for (int c = 0; c < LN_MAXV; ++c) {
       int ch = lane + 64 * c;
       if (ch < nch) {
         v[c] = *reinterpret_cast<const u16x8*>(xr + 8 * ch);
-        if (res) {
+        if constexpr (DROP) {
+          const u16x8 rv = *reinterpret_cast<const u16x8*>(res + (size_t)row * D + 8 * ch);
+#pragma unroll
+          for (int g = 0; g < 2; ++g) {
+            const unsigned wd = drop_fmix32(pk ^ ((unsigned)(2 * ch + g) * 0x85EBCA77u));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float hv = drop_byte(wd, e) >= drop.T ? bf2f(rv[4 * g + e]) * dsc : 0.f;
+              v[c][4 * g + e] = f2bf(bf2f(v[c][4 * g + e]) + hv);
+            }
+          }
+          *reinterpret_cast<u16x8*>(xs + (size_t)row * D + 8 * ch) = v[c];
+        } else if (res) {
           const u16x8 rv = *reinterpret_cast<const u16x8*>(res + (size_t)row * D + 8 * ch);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[c][e] = f2bf(bf2f(v[c][e]) + bf2f(rv[e]));
@@ -308,13 +331,22 @@ __global__ void __launch_bounds__(LN_T) ln_fwd_kernel(const u16* __restrict__ x,
 
 // dx = rstd * (g*w - mean(g*w) - xhat * mean(g*w*xhat)) (+ gadd: the residual-path gradient of
 // a fused add + LayerNorm, summed in fp32 and rounded once); dw += g*xhat; db += g (per-block slabs)
-template <int LN_MAXV>
+// DROP (compile-time): the gradient of the dropped addend of a fused add + LayerNorm with residual dropout goes to a
+// second output in the same pass, dh = bf16(d * M * 256 / (256 - T)) from the fp32 d (not from the rounded dx)
+template <int LN_MAXV, bool DROP = false>
 __global__ void __launch_bounds__(LN_T) ln_bwd_kernel(const u16* __restrict__ x, const u16* __restrict__ w,
                                                       const u16* __restrict__ gy, const float* __restrict__ mean,
                                                       const float* __restrict__ rstd, const u16* __restrict__ gadd,
-                                                      u16* __restrict__ dx, float* __restrict__ part, int rows, int D) {
+                                                      u16* __restrict__ dx, float* __restrict__ part, int rows, int D,
+                                                      u16* __restrict__ dh, DropArgs drop, int S) {
   const int lane = threadIdx.x & 63, wv_id = threadIdx.x >> 6;
   const int nch = D / 8;
+  unsigned long long skey = 0;
+  float dsc = 1.f;
+  if constexpr (DROP) {
+    skey = drop_site_key(drop_eff_seed(drop.seed, drop.ctr), drop.site_layer);
+    dsc = drop_scale(drop.T);
+  }
   // per-thread partial dW/dB for the chunks this lane owns (reduced over the block's rows)
   float pw[LN_MAXV][8], pb[LN_MAXV][8];
 #pragma unroll
@@ -355,16 +387,36 @@ __global__ void __launch_bounds__(LN_T) ln_bwd_kernel(const u16* __restrict__ x,
     s1 = wave_sum(s1) / D;
     s2 = wave_sum(s2) / D;
     u16* dr = dx + (size_t)row * D;
+    unsigned pk = 0;
+    if constexpr (DROP)
+      pk = drop_row_key(skey, drop.sample0 + (unsigned)(row / S), 0) ^ ((unsigned)(row % S) * 0x9E3779B1u);
 #pragma unroll
     for (int c = 0; c < LN_MAXV; ++c) {
       int ch = lane + 64 * c;
       if (ch < nch) {
         const u16x8 wv = wc[c];
         u16x8 o;
+        if constexpr (DROP) {
+          u16x8 oh;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float xh = (bf2f(xv[c][e]) - mu) * rs;
-          o[e] = f2bf(rs * (bf2f(gv[c][e]) * bf2f(wv[e]) - s1 - xh * s2) + bf2f(av[c][e]));
+          for (int g = 0; g < 2; ++g) {
+            const unsigned wd = drop_fmix32(pk ^ ((unsigned)(2 * ch + g) * 0x85EBCA77u));
+#pragma unroll
+            for (int e4 = 0; e4 < 4; ++e4) {
+              const int e = 4 * g + e4;
+              float xh = (bf2f(xv[c][e]) - mu) * rs;
+              const float d = rs * (bf2f(gv[c][e]) * bf2f(wv[e]) - s1 - xh * s2) + bf2f(av[c][e]);
+              o[e] = f2bf(d);
+              oh[e] = f2bf(drop_byte(wd, e4) >= drop.T ? d * dsc : 0.f);
+            }
+          }
+          *reinterpret_cast<u16x8*>(dh + (size_t)row * D + 8 * ch) = oh;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float xh = (bf2f(xv[c][e]) - mu) * rs;
+            o[e] = f2bf(rs * (bf2f(gv[c][e]) * bf2f(wv[e]) - s1 - xh * s2) + bf2f(av[c][e]));
+          }
         }
         *reinterpret_cast<u16x8*>(dr + 8 * ch) = o;
       }
@@ -540,7 +592,7 @@ void layernorm_fwd_bf16(const void* x, const void* w, const void* b, void* y, fl
   hipLaunchKernelGGL((ln_fwd_kernel<V>), dim3(blocks), dim3(LN_T), 0, stream, reinterpret_cast<const u16*>(x), \
                      reinterpret_cast<const u16*>(res), reinterpret_cast<const u16*>(w),                         \
                      reinterpret_cast<const u16*>(b), reinterpret_cast<u16*>(xs), reinterpret_cast<u16*>(y),     \
-                     mean, rstd, rows, D, eps)
+                     mean, rstd, rows, D, eps, DropArgs{}, 1)
   if (D <= 512) LNF(1);
   else if (D <= 1024) LNF(2);
   else if (D <= 2048) LNF(4);
@@ -555,7 +607,7 @@ void layernorm_bwd_bf16(const void* x, const void* w, const void* gy, const floa
 #define LNB(V)                                                                                                 \
   hipLaunchKernelGGL((ln_bwd_kernel<V>), dim3(blocks), dim3(LN_T), 0, stream, reinterpret_cast<const u16*>(x), \
                      reinterpret_cast<const u16*>(w), reinterpret_cast<const u16*>(gy), mean, rstd, nullptr,    \
-                     reinterpret_cast<u16*>(dx), workspace, rows, D)
+                     reinterpret_cast<u16*>(dx), workspace, rows, D, nullptr, DropArgs{}, 1)
   if (D <= 512) LNB(1);
   else if (D <= 1024) LNB(2);
   else if (D <= 2048) LNB(4);
@@ -575,7 +627,47 @@ void layernorm_bwd_bf16_accum(const void* x, const void* w, const void* gy, cons
 #define LNB(V)                                                                                                 \
   hipLaunchKernelGGL((ln_bwd_kernel<V>), dim3(blocks), dim3(LN_T), 0, stream, reinterpret_cast<const u16*>(x), \
                      reinterpret_cast<const u16*>(w), reinterpret_cast<const u16*>(gy), mean, rstd,             \
-                     reinterpret_cast<const u16*>(gadd), reinterpret_cast<u16*>(dx), workspace, rows, D)
+                     reinterpret_cast<const u16*>(gadd), reinterpret_cast<u16*>(dx), workspace, rows, D, nullptr,  \
+                     DropArgs{}, 1)
+  if (D <= 512) LNB(1);
+  else if (D <= 1024) LNB(2);
+  else if (D <= 2048) LNB(4);
+  else LNB(8);
+#undef LNB
+  hipLaunchKernelGGL(slab_sum_bf16_kernel, dim3((2 * D + 63) / 64), dim3(1024), 0, stream, workspace, blocks, 2 * D, D,
+                     reinterpret_cast<u16*>(gw), reinterpret_cast<u16*>(gb));
+}
+
+void add_layernorm_drop_fwd_bf16(const void* x, const void* h, const void* w, const void* b, void* xs, void* y,
+                                 float* mean, float* rstd, int rows, int D, int S, float eps, const DropArgs& drop,
+                                 hipStream_t stream) {
+  if (rows <= 0) return;
+  if (!drop.T || !h || !xs || S <= 0) abort();  // host contract
+  int blocks = (rows + 3) / 4;
+  if (blocks > 4096) blocks = 4096;
+#define LNF(V)                                                                                                        \
+  hipLaunchKernelGGL((ln_fwd_kernel<V, true>), dim3(blocks), dim3(LN_T), 0, stream, reinterpret_cast<const u16*>(x),  \
+                     reinterpret_cast<const u16*>(h), reinterpret_cast<const u16*>(w),                                \
+                     reinterpret_cast<const u16*>(b), reinterpret_cast<u16*>(xs), reinterpret_cast<u16*>(y), mean,    \
+                     rstd, rows, D, eps, drop, S)
+  if (D <= 512) LNF(1);
+  else if (D <= 1024) LNF(2);
+  else if (D <= 2048) LNF(4);
+  else LNF(8);
+#undef LNF
+}
+
+void layernorm_bwd_bf16_accum_drop(const void* x, const void* w, const void* gy, const float* mean, const float* rstd,
+                                   void* dx, void* dh, float* workspace, void* gw, void* gb, int rows, int D, int S,
+                                   const void* gadd, const DropArgs& drop, hipStream_t stream) {
+  if (rows <= 0) return;
+  if (!drop.T || !dh || S <= 0) abort();  // host contract
+  const int blocks = layernorm_bwd_blocks(rows);
+#define LNB(V)                                                                                                       \
+  hipLaunchKernelGGL((ln_bwd_kernel<V, true>), dim3(blocks), dim3(LN_T), 0, stream, reinterpret_cast<const u16*>(x), \
+                     reinterpret_cast<const u16*>(w), reinterpret_cast<const u16*>(gy), mean, rstd,                   \
+                     reinterpret_cast<const u16*>(gadd), reinterpret_cast<u16*>(dx), workspace, rows, D,              \
+                     reinterpret_cast<u16*>(dh), drop, S)
   if (D <= 512) LNB(1);
   else if (D <= 1024) LNB(2);
   else if (D <= 2048) LNB(4);

@@ -11,11 +11,18 @@ Linear layers (ops/linear.py) and LayerNorms accumulate their weight/bias gradie
 into the flat gradient buffer (GEMM beta = 1, in-place bf16 reductions) instead of
 materialise-then-add. Parameter names follow the common GPT-2 layout (wte, wpe, h.{i}.ln_1, h.{i}.attn.c_attn,
 h.{i}.attn.c_proj, h.{i}.ln_2, h.{i}.mlp.c_fc, h.{i}.mlp.c_proj, ln_f, lm_head).
+
+Dropout (GPT-2's recipe: embedding, attention probabilities, both residual branches) draws its masks from a counter
+hash (csrc/kernels/dropout_hash.h, twin in ops/reference.py) keyed by the run's seed, the engine's step counter, the
+site, the global layer, the dataset index of the sample, the global head and the coordinates inside the sample: the
+masks do not depend on the micro-batch split, the pipeline placement or the tensor-parallel rank. Probabilities are
+quantised to T / 256 (``GPT2Config.effective_pdrop``).
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -23,8 +30,10 @@ import torch.nn.functional as F
 
 from .base import ModelSpec, PipelineStage
 from ..ops.linear import Linear, linear, lm_head, mlp_gelu
-from ..ops.transformer import (LayerNorm, add_layer_norm, causal_attention, cross_entropy_sum, embedding, gelu,
-                               layer_norm_pass)
+from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
+                             dropout_threshold)
+from ..ops.transformer import (Drop, LayerNorm, add_layer_norm, causal_attention, cross_entropy_sum, dropout_add,
+                               embedding, gelu, layer_norm_pass)
 from ..parallel.tp import TPContext, column_slice, copy_to_tp, reduce_from_tp, shard_parameter
 
 
@@ -35,7 +44,29 @@ class GPT2Config:
     n_embd: int = 768
     vocab_size: int = 50257
     block_size: int = 1024
-    dropout: float = 0.0
+    dropout: float = 0.0  # sets the three probabilities below where they are not given
+    embd_pdrop: Optional[float] = None   # on wte[tok] + wpe[pos]
+    attn_pdrop: Optional[float] = None   # on the attention probabilities
+    resid_pdrop: Optional[float] = None  # on each block's attention and MLP output before the residual add
+
+    def __post_init__(self):
+        for f in ("embd_pdrop", "attn_pdrop", "resid_pdrop"):
+            if getattr(self, f) is None:
+                setattr(self, f, float(self.dropout))
+            dropout_threshold(getattr(self, f))  # range check
+
+    def thresholds(self) -> dict:
+        """site -> T = round(256 p) (0: off)."""
+        return {f: dropout_threshold(getattr(self, f)) for f in ("embd_pdrop", "attn_pdrop", "resid_pdrop")}
+
+    def effective_pdrop(self) -> dict:
+        """The probabilities the kernels apply: T / 256."""
+        return {f: t / 256.0 for f, t in self.thresholds().items()}
+
+
+def dropout_seed(seed: int) -> int:
+    """The run's dropout seed (63 bits) from the run seed: the same on every rank."""
+    return ((int(seed) + 1) * 0x9E3779B97F4A7C15 ^ 0xD1B54A32D192ED03) & ((1 << 63) - 1)
 
 
 class CausalSelfAttention(nn.Module):
@@ -44,6 +75,7 @@ class CausalSelfAttention(nn.Module):
         self.c_attn = Linear(cfg.n_embd, 3 * cfg.n_embd)
         self.c_proj = Linear(cfg.n_embd, cfg.n_embd)
         self.n_head = cfg.n_head
+        self.head0 = 0  # global index of this rank's first head
         self.tp: TPContext = None
 
     def shard_tp(self, tp: TPContext):
@@ -56,13 +88,17 @@ class CausalSelfAttention(nn.Module):
         shard_parameter(self.c_attn, "bias", 0, idx)
         shard_parameter(self.c_proj, "weight", 1, cols)
         self.n_head //= tp.size
+        self.head0 = tp.rank * self.n_head
         self.tp = tp
 
-    def forward(self, x):
-        # HIP flash attention (bf16, head_dim 64) on ROCm; PyTorch SDPA elsewhere
+    def forward(self, x, drop: Optional[Drop] = None):
+        # HIP flash attention (bf16, head_dim 64) on ROCm; PyTorch SDPA elsewhere. drop: attention dropout of this
+        # layer and call; the mask is keyed by the global head index
+        if drop is not None:
+            drop = Drop(drop.T, drop.seed, drop.ctr, drop.site, drop.layer, drop.sample0, self.head0)
         if self.tp is None:
-            return self.c_proj(causal_attention(self.c_attn(x), self.n_head))
-        a = causal_attention(self.c_attn(copy_to_tp(x, self.tp)), self.n_head)
+            return self.c_proj(causal_attention(self.c_attn(x), self.n_head, drop))
+        a = causal_attention(self.c_attn(copy_to_tp(x, self.tp)), self.n_head, drop)
         return reduce_from_tp(linear(a, self.c_proj.weight), self.tp) + self.c_proj.bias
 
 
@@ -101,6 +137,14 @@ class Block(nn.Module):
 
 
 class GPT2Stage(PipelineStage):
+    """One pipeline stage of GPT-2.
+
+    Dropout: the engine's hooks ``fwd`` / ``head_fwd`` hand the call's dataset offset (``ctx["sample0"]``) and train flag
+    to ``forward`` through the attributes ``_sample0`` / ``_drop_call``, set for the duration of the call and reset after
+    it (the engine calls a stage from one thread). A direct ``stage(x)`` outside those hooks, with the module in
+    training mode and some probability > 0, draws the masks of samples 0, 1, ... (``sample0 = 0``): call it through
+    ``fwd`` with ``ctx["sample0"]`` set when the rows are other samples."""
+
     def __init__(self, cfg: GPT2Config, stage_id: int, num_stages: int):
         super().__init__()
         if cfg.n_layer % num_stages:
@@ -119,7 +163,36 @@ class GPT2Stage(PipelineStage):
             # the vocabulary padded to a multiple of 64 rows in the flat storage (zero rows, zero gradient): the
             # lm_head's three GEMMs run on the hand-written kernels as 50304-wide GEMMs (ops/linear.py lm_head)
             self.flat_row_multiple = {"lm_head.weight": 64}
+        # dropout: the engine hands over its device step counter (rng_step) and each call's dataset offset
+        # (ctx["sample0"]) only when some probability is on; with all three at 0 nothing below runs
+        self._drop_t = cfg.thresholds()
+        self.uses_rng_step = self.uses_sample0 = any(self._drop_t.values())
+        self.drop_seed = dropout_seed(0)
+        self._sample0, self._drop_call = 0, True
         self._init()
+
+    def set_run_seed(self, seed: int):
+        """The engine's run seed: every rank derives the same dropout seed from it."""
+        self.drop_seed = dropout_seed(seed)
+
+    def _drop(self, which: str, site: int, layer: int) -> Optional[Drop]:
+        t = self._drop_t[which]
+        if not t or not (self.training and self._drop_call):
+            return None
+        return Drop(t, self.drop_seed, getattr(self, "rng_step", None), site, layer, self._sample0)
+
+    def _with_call(self, ctx, train, fn):
+        """Run a stage hook with the call's dataset offset and train flag visible to forward()."""
+        self._sample0, self._drop_call = int(ctx.get("sample0", 0)), bool(train)
+        try:
+            return fn()
+        finally:
+            self._sample0, self._drop_call = 0, True
+
+    def fwd(self, x, ctx, train):
+        if not self.uses_sample0:
+            return super().fwd(x, ctx, train)
+        return self._with_call(ctx, train, lambda: PipelineStage.fwd(self, x, ctx, train))
 
     supports_tp = True
 
@@ -144,6 +217,11 @@ class GPT2Stage(PipelineStage):
 
     # ---- last stage: fused vocab cross-entropy (no fp32 copy of the [tokens, 50257] logits) --
     def head_fwd(self, x, target, ctx, train, loss_scale, stats=None):
+        if not self.uses_sample0:
+            return self._head_fwd(x, target, ctx, train, loss_scale)
+        return self._with_call(ctx, train, lambda: self._head_fwd(x, target, ctx, train, loss_scale))
+
+    def _head_fwd(self, x, target, ctx, train, loss_scale):
         if not train:
             with torch.no_grad():
                 logits = self(x)
@@ -166,7 +244,7 @@ class GPT2Stage(PipelineStage):
 
     def forward(self, x):
         if self.stage_id == 0:  # token + position embedding (HIP gather, deterministic backward)
-            x = embedding(x, self.wte.weight, self.wpe.weight)
+            x = embedding(x, self.wte.weight, self.wpe.weight, self._drop("embd_pdrop", DROP_SITE_EMBD, 0))
         last = self.stage_id == self.num_stages - 1
         blocks = list(self.h.values())
         if not blocks:
@@ -174,14 +252,18 @@ class GPT2Stage(PipelineStage):
         # each residual add is fused into the LayerNorm that reads its sum (ln_2 of the same block,
         # ln_1 of the next, ln_f at the end); the block maths is exactly Block.forward
         x, y = layer_norm_pass(x, blocks[0].ln_1)  # (x feeds ln_1 and the residual: one backward node for both)
+        layers = [int(k) for k in self.h.keys()]  # global layer indices h.{i}
         for i, blk in enumerate(blocks):
-            x, y = add_layer_norm(x, blk.attn(y), blk.ln_2)
+            li = layers[i]
+            a = blk.attn(y, self._drop("attn_pdrop", DROP_SITE_ATTN, li))
+            x, y = add_layer_norm(x, a, blk.ln_2, self._drop("resid_pdrop", DROP_SITE_RESID_ATTN, li))
             m = blk.mlp(y)
             nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
+            dm = self._drop("resid_pdrop", DROP_SITE_RESID_MLP, li)
             if nxt is None:
-                x = x + m
+                x = x + m if dm is None else dropout_add(x, m, dm)
             else:
-                x, y = add_layer_norm(x, m, nxt)
+                x, y = add_layer_norm(x, m, nxt, dm)
         return lm_head(y, self.lm_head.weight) if last else x
 
 

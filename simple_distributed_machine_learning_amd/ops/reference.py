@@ -202,3 +202,90 @@ def ref_cnn_stage1_logp(x, w1, b1, w2, b2, seed: int, sample0: int, p: float, dr
     if drop:
         h = h * dropout_keep_scale(seed, sample0, x.shape[0], 50, p).to(h.device)
     return F.log_softmax(F.linear(h, w2, b2), dim=1)
+
+
+# ---- GPT-2 dropout masks (csrc/kernels/dropout_hash.h) --------------------------------------
+# The host twin of the kernels' counter hash, in plain torch int64 ops (two's-complement wrap-around stands for the
+# kernels' unsigned arithmetic), so it runs on the CPU and on a device tensor and agrees with the kernels bit for bit.
+# A mask bit is a function of (seed, step counter, site, global layer, dataset index of the sample, global head,
+# coordinates inside the sample) and nothing else.
+DROP_SITE_EMBD, DROP_SITE_ATTN, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP = 1, 2, 3, 4
+_M32 = 0xFFFFFFFF
+_GOLDEN64 = 0x9E3779B97F4A7C15
+
+
+def _s64(v: int) -> int:
+    """The int64 with the bits of v mod 2^64."""
+    v &= _M64
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _lsr64(x, s: int):
+    return (x >> s) & ((1 << (64 - s)) - 1)
+
+
+def _splitmix64(x):
+    x = x + _s64(_GOLDEN64)
+    x = (x ^ _lsr64(x, 30)) * _s64(0xBF58476D1CE4E5B9)
+    x = (x ^ _lsr64(x, 27)) * _s64(0x94D049BB133111EB)
+    return x ^ _lsr64(x, 31)
+
+
+def _fmix32(h):
+    """Murmur3's finaliser on int64 tensors holding 32-bit values."""
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & _M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & _M32
+    return h ^ (h >> 16)
+
+
+def dropout_threshold(p: float) -> int:
+    """T = round(256 p), 1..255 for p > 0: a value is kept iff its mask byte >= T (effective p = T / 256)."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability must be in [0, 1), got {p}")
+    if p == 0.0:
+        return 0
+    return min(255, max(1, int(math.floor(256.0 * p + 0.5))))
+
+
+def dropout_scale(T: int) -> float:
+    """256 / (256 - T) as the kernels compute it (one fp32 division)."""
+    return float(torch.tensor(256.0, dtype=torch.float32) / torch.tensor(float(256 - T), dtype=torch.float32))
+
+
+def gpt2_dropout_row_keys(seed: int, ctr, site: int, layer: int, samples, heads):
+    """32-bit row keys (int64 tensor, broadcast of ``samples`` and ``heads``). ``ctr``: the int64 step-counter tensor
+    (read on its device, no host sync) or None for counter 0."""
+    eff = torch.as_tensor(_s64(seed), dtype=torch.int64, device=samples.device)
+    if ctr is not None:
+        eff = eff + _s64(_GOLDEN64) * ctr.reshape(-1)[0].to(samples.device)
+    skey = _splitmix64(eff ^ ((int(site) << 32) | int(layer)))
+    return _lsr64(_splitmix64(skey ^ ((samples << 32) | heads)), 32)
+
+
+def gpt2_dropout_keep(rkey, na: int, nb: int, T: int):
+    """keep[..., a, b] (bool) for row keys ``rkey`` [...]: byte (b & 3) of fmix32(rkey ^ a * 0x9E3779B1 ^
+    (b >> 2) * 0x85EBCA77) >= T."""
+    dev = rkey.device
+    a = (torch.arange(na, dtype=torch.int64, device=dev) * 0x9E3779B1) & _M32
+    b = torch.arange(nb, dtype=torch.int64, device=dev)
+    b4 = ((b >> 2) * 0x85EBCA77) & _M32
+    word = _fmix32(rkey[..., None, None] ^ a[:, None] ^ b4[None, :])
+    return ((word >> (8 * (b & 3))) & 255) >= T
+
+
+def gpt2_attn_keep(seed: int, ctr, layer: int, sample0: int, B: int, head0: int, H: int, S: int, T: int,
+                   device=None):
+    """[B, H, S, S] keep mask of the attention probabilities (query, key) of samples sample0.. and heads head0.. ."""
+    dev = device if device is not None else (ctr.device if ctr is not None else "cpu")
+    smp = torch.arange(sample0, sample0 + B, dtype=torch.int64, device=dev)[:, None]
+    hd = torch.arange(head0, head0 + H, dtype=torch.int64, device=dev)[None, :]
+    return gpt2_dropout_keep(gpt2_dropout_row_keys(seed, ctr, DROP_SITE_ATTN, layer, smp, hd), S, S, T)
+
+
+def gpt2_site_keep(seed: int, ctr, site: int, layer: int, sample0: int, B: int, S: int, C: int, T: int, device=None):
+    """[B, S, C] keep mask of an element-wise site (position, channel)."""
+    dev = device if device is not None else (ctr.device if ctr is not None else "cpu")
+    smp = torch.arange(sample0, sample0 + B, dtype=torch.int64, device=dev)
+    return gpt2_dropout_keep(gpt2_dropout_row_keys(seed, ctr, site, layer, smp, torch.zeros_like(smp)), S, C, T)

@@ -195,6 +195,14 @@ class PipelineEngine:
             if getattr(m, "uses_rng_step", False):
                 m.rng_step = self.step_ctr
                 self._uses_rng = True
+            if hasattr(m, "set_run_seed"):  # counter-hash dropout: one seed for the run, the same on every rank
+                m.set_run_seed(seed)
+            if getattr(m, "uses_sample0", False) and self.kind == "rotate":
+                # the masks are keyed by each row's dataset index, passed as one offset per call; rotate's all-to-all
+                # waves put rows of several owners into one call, which is then no contiguous sample range
+                raise ValueError(f"{spec.name}: dropout is not supported with schedule 'rotate' (a call's rows are not "
+                                 "one contiguous sample range); use gpipe, 1f1b or chimera, or set the dropout "
+                                 "probabilities to 0")
         self.optimizer_kind = optimizer
         if optimizer == "adamw":
             self.optimizer = FusedAdamW(self.flat, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
@@ -478,6 +486,8 @@ class PipelineEngine:
                     prev_local = sched.task_rank(ins.mb, ins.stage - 1) == self.mesh.pp_rank
                     x = take((PL_ACT, ins.pipe, ins.stage - 1, ins.mb), prev_local)
                 ctx = ctxs.setdefault((ins.pipe, ins.stage, ins.mb), {})
+                if getattr(mod, "uses_sample0", False):  # dropout masks are keyed by the rows' dataset indices
+                    ctx["sample0"] = off
                 if mod.is_last:
                     tgt = dataset.targets(off, mbsz)
                     if tgt.device != dev:

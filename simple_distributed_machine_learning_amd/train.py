@@ -23,7 +23,8 @@ import torch
 
 from . import cli
 from .data import IdxMNIST, SyntheticMNIST, SyntheticTokens, batch_ranges
-from .models import DEFAULT_STAGES, get_model_spec
+from .ops.reference import dropout_threshold
+from .models import DEFAULT_STAGES, GPT2_DROPOUT_FLAGS, get_model_spec
 from .parallel import PipelineEngine, init_mesh, shutdown
 from .utils.checkpoint import load_checkpoint, save_checkpoint
 from .utils.failure import Heartbeat
@@ -60,6 +61,7 @@ def make_datasets(args, spec, device):
 
 def run(args) -> dict:
     cli.export_env(args)
+    pdrop = {k: getattr(args, k, 0.0) for k in GPT2_DROPOUT_FLAGS}
     device = _device(args)
     stages = args.stages or DEFAULT_STAGES[args.model]
     tp = max(1, getattr(args, "tp", 1))
@@ -77,17 +79,24 @@ def run(args) -> dict:
     if dt is None and args.model == "resnet18" and device.type == "cuda":
         dt = torch.bfloat16  # the ResNet's GPU kernels are bf16 channels-last (ops/conv.py); fp32 is the CPU path
     kw = {"dtype": dt} if dt is not None and args.model in ("resnet18", "gpt2_tiny") else {}
-    spec = get_model_spec(args.model, stages, eval_dropout=bool(args.eval_dropout), seq_len=args.seq_len,
-                          dropout=getattr(args, "dropout", 0.5), **kw)
-    if dt is not None and spec.param_dtype != dt:
-        raise SystemExit(f"--dtype {args.dtype} is not supported for --model {args.model}")
-    engine = PipelineEngine(spec, mesh, schedule_kind=args.schedule, num_microbatches=args.microbatches,
-                            lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, seed=args.seed,
-                            debug_sync=args.debug_sync, timing=getattr(args, "timing", False),
-                            optimizer=getattr(args, "optimizer", "sgd"),
-                            betas=(getattr(args, "beta1", 0.9), getattr(args, "beta2", 0.999)),
-                            eps=getattr(args, "eps", 1e-8), clip_grad=getattr(args, "clip_grad", 0.0),
-                            lr_schedule=cli.lr_schedule_of(args) if hasattr(args, "lr_schedule") else None)
+    try:
+        spec = get_model_spec(args.model, stages, eval_dropout=bool(args.eval_dropout), seq_len=args.seq_len,
+                              dropout=getattr(args, "dropout", 0.5), **pdrop, **kw)
+        if dt is not None and spec.param_dtype != dt:
+            raise SystemExit(f"--dtype {args.dtype} is not supported for --model {args.model}")
+        engine = PipelineEngine(spec, mesh, schedule_kind=args.schedule, num_microbatches=args.microbatches,
+                                lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, seed=args.seed,
+                                debug_sync=args.debug_sync, timing=getattr(args, "timing", False),
+                                optimizer=getattr(args, "optimizer", "sgd"),
+                                betas=(getattr(args, "beta1", 0.9), getattr(args, "beta2", 0.999)),
+                                eps=getattr(args, "eps", 1e-8), clip_grad=getattr(args, "clip_grad", 0.0),
+                                lr_schedule=cli.lr_schedule_of(args) if hasattr(args, "lr_schedule") else None)
+    except ValueError as e:
+        # GPT-2 dropout with another model is refused by the model registry, with --schedule rotate by the engine
+        # (every rank alike): end with their message instead of a traceback
+        if not any(pdrop.values()):
+            raise
+        raise SystemExit(str(e))
     torch.manual_seed(args.seed * 7 + mesh.rank)  # dropout streams (reference: unseeded)
     if spec.input_kind == "tokens" and device.type == "cuda" and os.environ.get("SDML_GPT2_GEMM") == "lib":
         from .utils.tuned_gemm import use_tuned_gemms
@@ -96,6 +105,12 @@ def run(args) -> dict:
     train_ds, test_ds = make_datasets(args, spec, device)
     metrics = JsonlMetrics(args.metrics if mesh.is_master() else None, mesh.rank)
     master = mesh.is_master()
+    if any(pdrop.values()):  # the probabilities the kernels apply: round(256 p) / 256
+        eff = {k: dropout_threshold(v) / 256.0 for k, v in pdrop.items()}
+        if master:
+            print("[sdml] GPT-2 dropout, effective probabilities: " + ", ".join(f"{k}={v:.6f}" for k, v in eff.items()),
+                  flush=True)
+        metrics.log(event="config", model=args.model, **eff)
     B = args.batch_size
     GB = B * engine.data_shards  # one optimizer step consumes this many samples
     TB = args.test_batch_size or B

@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"])
     ap.add_argument("--clip_grad", type=float, default=0.0, help="adamw: global gradient-norm clip (0: off)")
     ap.add_argument("--weight_decay", type=float, default=0.0)
+    for f in ("embd_pdrop", "attn_pdrop", "resid_pdrop"):
+        ap.add_argument(f"--{f}", type=float, default=0.0, help="gpt2: dropout probability of this site")
     a = ap.parse_args()
     kind, M, B, S = DEFAULTS[a.config]
     small = a.config in ("mlp", "ref_cnn") and (a.batch or B) <= 128
@@ -76,7 +78,8 @@ def main():
         # the hand-written conv / BatchNorm kernels are bf16 channels-last (fp32 runs on MIOpen):
         # 107K vs 27.2K samples/s on one MI355X
         dt = torch.bfloat16
-    spec = get_model_spec(a.config, stages, seq_len=S, **({"dtype": dt} if dt is not None else {}))
+    pdrop = {f: getattr(a, f) for f in ("embd_pdrop", "attn_pdrop", "resid_pdrop")}
+    spec = get_model_spec(a.config, stages, seq_len=S, **pdrop, **({"dtype": dt} if dt is not None else {}))
     opt = {} if a.optimizer == "sgd" else {"optimizer": a.optimizer, "clip_grad": a.clip_grad}
     eng = PipelineEngine(spec, mesh, schedule_kind=kind, num_microbatches=M, lr=0.01 if a.optimizer == "sgd" else 3e-4,
                          momentum=0.5, weight_decay=a.weight_decay, seed=1, **opt)
@@ -132,7 +135,7 @@ def main():
         print(json.dumps({"config": a.config, "schedule": kind, "stages": stages, "ranks": world, "tp": a.tp,
                           "microbatches": M, "batch": GB, "seq_len": S, "dtype": str(spec.param_dtype), "graph": a.graph or False, "tuned_gemms": tuned,
                           "pixels": a.pixels, "optimizer": a.optimizer, "clip_grad": a.clip_grad,
-                          "weight_decay": a.weight_decay,
+                          "weight_decay": a.weight_decay, **pdrop,
                           "value": round(GB * per_sample * a.steps / el, 1), "unit": unit,
                           "ms_per_step": round(el / a.steps * 1e3, 3), "loss": round(l / max(1, n), 4),
                           "bubble_model": round(eng.schedule(M, False).bubble_fraction(), 3)}))
