@@ -45,16 +45,12 @@
 
 #include "dropout_hash.h"
 #include "kernels.h"
+#include "mma_prims.h"
 
 namespace sdml {
 namespace {
 
-typedef unsigned short u16;
-typedef __attribute__((ext_vector_type(8))) short bf16x8;  // MFMA operand (8 x bf16)
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-typedef u16 u16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HD = 64;             // head dim
 constexpr int QW = 32;             // queries per wave
@@ -101,10 +97,6 @@ __device__ __forceinline__ int swz(int r, int ch) {
 // row fragment (A/B operand with k = d): element j = X[row][16t + 8h + j]
 __device__ __forceinline__ bf16x8 rowf(const u16* X, int row, int t, int h) {
   return *reinterpret_cast<const bf16x8*>(X + swz(row, 2 * t + h));
-}
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ s16x4 ds_tr16(const u16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 // transposed fragment in the accumulator k-order: element j = X[k0 + 8(j>>2) + 4h + (j&3)][c0 + (lane&31)]
 // (k0 % 8 == 0, c0 % 32 == 0). Two ds_read_b64_tr_b16: each 16-lane group g reads rows

@@ -24,15 +24,11 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "mma_prims.h"
+#include "tile_order.h"
 
 namespace sdml {
 namespace {
-
-typedef unsigned short u16;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int NT = 512, BM = 256, BK = 64;
 
@@ -220,12 +216,7 @@ __global__ void __launch_bounds__(NT) conv3x3_fwd_kernel(ConvArgs a) {
   constexpr int NB = BN * 8 / NT;        // B chunks per thread: 2 or 1
   __shared__ __attribute__((aligned(16))) u16 smem[2 * (AI + BI)];
   const int ntiles = a.tiles_m * a.tiles_n;
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (ntiles >= 16) {  // XCD-aware bijective remap: neighbouring pixel tiles share an L2
-    const int q = ntiles / 8, r = ntiles % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, ntiles);  // neighbouring pixel tiles share an L2
   const int tn = wg % a.tiles_n, tm = wg / a.tiles_n;  // the Cout tiles of a pixel tile are adjacent
   const int m0 = tm * BM, n0 = tn * BN;
   const int K = a.KS * a.KS * a.C;
@@ -372,12 +363,7 @@ __global__ void __launch_bounds__(NT) conv_dgrad_s2_kernel(DgArgs a) {
   constexpr int AI = BM * BK, BI = BN * BK;
   constexpr int NB = BN * 8 / NT;
   __shared__ __attribute__((aligned(16))) u16 smem[2 * (AI + BI)];
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (a.tiles >= 16) {  // XCD-aware bijective remap
-    const int q = a.tiles / 8, r = a.tiles % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, a.tiles);
   int j = 0;
   DgClass c = dg_class(0, a.Nb, a.H, a.W, a.KS, a.P, a.Cg, a.Cn, a.tiles_n);
   for (int jj = 1; jj < 4; ++jj) {
@@ -535,12 +521,7 @@ __global__ void __launch_bounds__(NT, halo_occ(BN, HL)) conv3x3_halo_kernel(Conv
   u16* const HB[2] = {dsm, dsm + (nhb - 1) * HR * 64};
   u16* const BB[2] = {dsm + nhb * HR * 64, dsm + nhb * HR * 64 + BI};
   const int ntiles = a.tiles_m * a.tiles_n;
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (ntiles >= 16) {
-    const int q = ntiles / 8, r = ntiles % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, ntiles);
   const int tn = wg % a.tiles_n, tm = wg / a.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int K = 9 * a.C;
@@ -661,11 +642,7 @@ __global__ void __launch_bounds__(NT, halo_occ(BN, HL)) conv3x3_halo_kernel(Conv
 
 // ---- weight gradient: dw[co][tap][ci] (fp32 slabs) = sum_p dy[p][co] x[p + off(tap)][ci] ---------
 // tile 128 (co) x 128 (tap, ci), K-step 64 pixels; both operands k-major images [64][128] read by
-// ds_read_b64_tr_b16 (same image/swizzle as gemm_bf16_wgrad.hip)
-__device__ __forceinline__ int km_off(int k, int c) { return k * 128 + 8 * (c ^ (((k & 3) << 2) | ((k >> 2) & 3))); }
-__device__ __forceinline__ s16x4 ds_tr16(const u16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
+// ds_read_b64_tr_b16 (mma_prims.h's km_off image, as gemm_bf16_wgrad.hip)
 __device__ __forceinline__ bf16x8 trfrag(const u16* P, int c0, int s, int lane) {
   const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
   const int k = 16 * s + 8 * (g >> 1) + q;
@@ -697,12 +674,7 @@ __global__ void __launch_bounds__(NT) conv3x3_wgrad_kernel(WgArgs a) {
   __shared__ __attribute__((aligned(16))) u16 smem[2 * 2 * IMG];
   const int ntiles = a.tiles_m * a.tiles_n;
   const int nwg = ntiles * a.splits;
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int split = wg / ntiles, tile = wg % ntiles;
   const int tm = tile % a.tiles_m, tn = tile / a.tiles_m;
   const int m0 = tm * TMR, n0 = tn * 128;  // m: co, n: tap*C + ci
@@ -825,28 +797,9 @@ __global__ void __launch_bounds__(NT) conv3x3_wgrad_kernel(WgArgs a) {
 // the 32 KiB per K-step. A DMA instruction writes 4 image rows lane-linearly, so lane l owns rows
 // 4 wave + l/16 (+ 32) and the logical chunk (l % 16) ^ swz(row) of both images (swz(r) = swz(r + 32)).
 // Taps outside the image, pixels past the split and dy rows past it read a zero page in global memory
-// (a DMA cannot zero-fill). Fragments by inline-asm transposed reads (the builtin made the compiler wait
-// for every DMA in flight before each read), lgkmcnt waited explicitly.
+// (a DMA cannot zero-fill). Fragments by inline-asm transposed reads with explicit lgkmcnt waits (ds_tr16_asm and
+// lgkm_wait, mma_prims.h).
 __device__ __attribute__((aligned(16))) u16 g_zero16[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-
-__device__ __forceinline__ void glds16(const void* src, u16* lds_block) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_block, 16, 0, 0);
-}
-
-__device__ __forceinline__ s16x4 ds_tr16_asm(const u16* p) {
-  const unsigned a = (unsigned)(size_t)(const __attribute__((address_space(3))) u16*)p;
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(a));
-  return v;
-}
-
-template <int NR>
-__device__ __forceinline__ void lgkm_wait6(s16x4 (&f)[6]) {
-  asm volatile("s_waitcnt lgkmcnt(%6)"
-               : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5])
-               : "n"(NR));
-}
 
 // NSTG = 2: 64 KiB of LDS, two workgroups per CU, one K-step in flight; 3: 96 KiB, one workgroup, two
 template <int TMR, int NSTG>
@@ -858,12 +811,7 @@ __global__ void __launch_bounds__(NT) conv3x3_wgrad_dma_kernel(WgArgs a) {
   __shared__ __attribute__((aligned(16))) u16 smem[NSTG * BUF];
   const int ntiles = a.tiles_m * a.tiles_n;
   const int nwg = ntiles * a.splits;
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int split = wg / ntiles, tile = wg % ntiles;
   const int tm = tile % a.tiles_m, tn = tile / a.tiles_m;
   const int m0 = tm * TMR, n0 = tn * 128;
@@ -951,9 +899,9 @@ __global__ void __launch_bounds__(NT) conv3x3_wgrad_dma_kernel(WgArgs a) {
     for (int s = 0; s < 4; ++s) {
       if (s < 3) {
         rd(L, s + 1, fr[(s + 1) & 1]);
-        lgkm_wait6<NR>(fr[s & 1]);
+        lgkm_wait<NR>(fr[s & 1]);
       } else {
-        lgkm_wait6<0>(fr[s & 1]);
+        lgkm_wait<0>(fr[s & 1]);
       }
       const s16x4* f = fr[s & 1];
       const bf16x8 bfr = {f[2 * TI][0], f[2 * TI][1], f[2 * TI][2], f[2 * TI][3],

@@ -38,17 +38,11 @@
 #include "gelu.h"
 #include "kernels.h"
 #include "lds_dma.h"
+#include "mma_prims.h"
 #include "tile_order.h"
 
 namespace sdml {
 namespace {
-
-typedef unsigned short u16;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int GT = 512, TM = 256, TN = 256, TK = 64;
 constexpr int A_BYTES = TM * TK * 2;     // 32 KiB
@@ -76,14 +70,6 @@ __device__ __forceinline__ u16 f2bf(float f) {
   __hip_bfloat16 h = __float2bfloat16(f);  // RNE, NaN-preserving
   return *reinterpret_cast<u16*>(&h);
 }
-
-__device__ __forceinline__ void glds16(const void* src, unsigned char* lds_block) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_block, 16, 0, 0);
-}
-
-__device__ __forceinline__ int rk_swz(int r) { return (r >> 1) & 7; }                          // [rows][64]
-__device__ __forceinline__ int kn_swz(int r) { return ((r & 3) | ((r >> 1) & 4)) << 1; }       // [64][256]
 
 // one stage: A tile rows m0.., k0..k0+63; B tile (NT: rows n0.., NN: k-rows k0.., columns n0..)
 template <int BL>
@@ -115,9 +101,6 @@ __device__ __forceinline__ void issue_stage(const GP& p, unsigned char* st, int 
 }
 
 __device__ __forceinline__ bf16x8 ld_b128(const unsigned char* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ s16x4 ds_tr16(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
 
 // the elementwise part of the epilogues on one 16-B row piece v (bf16(acc (+ bias)) of 8 columns gcol.. of row grow),
 // then its store (shared by the 8-wave and 4-wave kernels)
@@ -249,11 +232,7 @@ template <int BL, int EPI>
 __global__ void __launch_bounds__(GT) gemm_bf16_kernel(GP p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
   const int nwg = p.tiles_m * p.tiles_n;
-  int wg = blockIdx.x;
-  if (nwg >= 16) {  // XCD-aware bijective remap: blocks sharing an XCD get consecutive tile ids
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + wg / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   int tm, tn;
   tile_of(wg, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
   const int m0 = tm * TM, n0 = tn * TN;
@@ -391,11 +370,7 @@ __global__ void __launch_bounds__(GT) gemm_bf16_nt4_kernel(GP p) {
   constexpr int INFLIGHT = half_pieces<0, NJ>() + half_pieces<1, NJ>() + half_pieces<2, NJ>();
   __shared__ __attribute__((aligned(16))) unsigned char smem[NSLOT * HT];  // the epilogue reuses it
   const int nwg = p.tiles_m * p.tiles_n;
-  int wg = blockIdx.x;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + wg / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   int tm, tn;
   tile_of(wg, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
   const int m0 = tm * TM, n0 = tn * BN;
@@ -570,11 +545,7 @@ __global__ void __launch_bounds__(GT) gemm_bf16_nt4p_kernel(GP p) {
   const int ntiles = p.tiles_m * p.tiles_n;
   const int G = gridDim.x;
   auto tile_at = [&](int v, int& m0, int& n0) {
-    int wg = v;
-    if (ntiles >= 16) {
-      const int q = ntiles / 8, r = ntiles % 8, xcd = v % 8;
-      wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + v / 8;
-    }
+    const int wg = xcd_remap(v, ntiles);
     int tm, tn;
     tile_of(wg, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
     m0 = tm * TM;
@@ -796,11 +767,7 @@ template <int EPI>
 __global__ void __launch_bounds__(W4_GT, 1) gemm_bf16_w4_kernel(GP p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[W4_SMEM];
   const int nwg = p.tiles_m * p.tiles_n;
-  int wg = blockIdx.x;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + wg / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   int tm, tn;
   tile_of(wg, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
   const int m0 = tm * TM, n0 = tn * TN;
@@ -953,11 +920,7 @@ template <int EPI>
 __global__ void __launch_bounds__(T2_GT, 2) gemm_bf16_t2_kernel(GP p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[T2_NST * T2_STAGE];
   const int nwg = p.tiles_m * p.tiles_n;
-  int wg = blockIdx.x;
-  if (nwg >= 16) {  // XCD-aware bijective remap (as the kernels above)
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + wg / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   int tm, tn;
   tile_of(wg, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
   const int m0 = tm * T2_TM, n0 = tn * T2_TN;

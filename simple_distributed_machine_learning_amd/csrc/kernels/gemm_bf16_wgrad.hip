@@ -26,8 +26,11 @@
 //     wave-instruction, MI355X_MICROARCH.md LDS table) that made the staged loop LDS-bound are gone.
 //     The bias gradient's column sums are read back from the A images (4 ds_read_b128 per thread
 //     per K-step, in the tn == 0 blocks only).
-//   wgrad_kernel (any T; SDML_WGRAD_DMA=0): register-staged double buffer (the loads of K-step t+2
+//   wgrad_kernel (any T; knob WGRAD_DMA = 0): register-staged double buffer (the loads of K-step t+2
 //     are in flight while K-step t+1 is written to LDS), rows past T zeroed on the store.
+// The tile constants, the register tile (KmTile), the fragment reads (trfrag, read_substep) and the k-major image are
+// wgrad_tiles.h's, shared with gemm_f16x2.hip; the DMA loop's inline-asm reads and their waits are mma_prims.h's
+// (ds_tr16_asm, lgkm_wait: the note there says why asm).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,19 +39,13 @@
 #include <string>
 
 #include "kernels.h"
+#include "tile_order.h"
+#include "wgrad_tiles.h"
 
 namespace sdml {
 namespace {
 
-typedef unsigned short u16;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int NT = 512, BM = 256, BN = 128, BK = 64;
-constexpr int IMG = BK * 128;  // u16 per 128-column image
+constexpr int NT = WNT, BM = WBM, BN = WBN, BK = WBK;  // wgrad_tiles.h's block and tile
 
 struct WgParams {
   const u16* A;  // gy [T][lda]
@@ -64,62 +61,8 @@ struct WgParams {
                // panel: the lm_head's 1.6 GB dlogits, read once from HBM instead of once per column tile)
 };
 
-__device__ __forceinline__ int km_off(int k, int ch) { return k * 128 + 8 * (ch ^ (((k & 3) << 2) | ((k >> 2) & 3))); }
-
-__device__ __forceinline__ s16x4 ds_tr16(const u16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-
-// fragment of the 32-column block at c0 of a [64][128] image, k-substep s: element j = X[16s + 8h + j][c0 + lane&31]
-__device__ __forceinline__ bf16x8 trfrag(const u16* P, int c0, int s, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int k = 16 * s + 8 * (g >> 1) + q;
-  const int col = c0 + 16 * (g & 1) + 4 * p;
-  const s16x4 lo = ds_tr16(P + km_off(k, col >> 3) + (col & 7));
-  const s16x4 hi = ds_tr16(P + km_off(k + 4, col >> 3) + (col & 7));
-  bf16x8 f;
-  f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-  f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-  return f;
-}
-
 __device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
 __device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, static_cast<__bf16>(f)); }
-
-// a COLS-wide k-major tile (64 k x COLS) in registers: COLS/8 chunks of 16 B per k-row
-template <int COLS>
-struct KmTile {
-  static constexpr int CPR = COLS / 8;            // chunks per k-row
-  static constexpr int NV = BK * CPR / NT;        // chunks per thread
-  u16x8 v[NV];
-  // clamped loads (rows past T / cols past the end re-read valid memory; zeroed in store)
-  __device__ __forceinline__ void load(const u16* __restrict__ P, int ld, int cols, int c0, int k0, int T) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int id = threadIdx.x + NT * u;
-      const int k = min(k0 + id / CPR, T - 1);
-      const int c = min(c0 + 8 * (id % CPR), cols - 8);
-      v[u] = *reinterpret_cast<const u16x8*>(P + (size_t)k * ld + c);
-    }
-  }
-  // ROWSUM: colsum[e] += the 8 staged values of this thread's column chunk (every u of a
-  // thread has the same chunk index: NT is a multiple of CPR), k >= kend excluded
-  template <bool ROWSUM>
-  __device__ __forceinline__ void store(u16* L, int k0, int kend, float (&colsum)[8]) const {
-    const u16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int id = threadIdx.x + NT * u;
-      const int k = id / CPR, ch = id % CPR;
-      const u16x8 val = (k0 + k < kend) ? v[u] : z;
-      *reinterpret_cast<u16x8*>(L + (ch >> 4) * IMG + km_off(k, ch & 15)) = val;
-      if constexpr (ROWSUM) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) colsum[e] += bf2f(val[e]);
-      }
-    }
-  }
-};
 
 __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -180,12 +123,7 @@ __global__ void __launch_bounds__(NT) wgrad_kernel(WgParams p) {
   // tiles that share an A/B column panel land on one XCD's L2
   const int ntiles = p.tiles_m * p.tiles_n;
   const int nwg = ntiles * p.splits;
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int split = wg / ntiles, tile = wg % ntiles;
   const int tm = p.nfast ? tile / p.tiles_n : tile % p.tiles_m, tn = p.nfast ? tile % p.tiles_n : tile / p.tiles_m;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -211,9 +149,9 @@ __global__ void __launch_bounds__(NT) wgrad_kernel(WgParams p) {
   if (nk > 0) {
     ta.load(p.A, p.lda, p.M, m0, kbeg, p.T);
     tb.load(p.B, p.ldb, p.N, n0, kbeg, p.T);
-    if (do_bias) ta.template store<true>(smem, kbeg, kend, cs);
-    else ta.template store<false>(smem, kbeg, kend, dummy);
-    tb.template store<false>(smem + 2 * IMG, kbeg, kend, dummy);
+    if (do_bias) ta.template store<true, Bf16Ops>(smem, kbeg, kend, true, cs);
+    else ta.template store<false, Bf16Ops>(smem, kbeg, kend, false, dummy);
+    tb.template store<false, Bf16Ops>(smem + 2 * IMG, kbeg, kend, false, dummy);
     ta.load(p.A, p.lda, p.M, m0, kbeg + BK, p.T);
     tb.load(p.B, p.ldb, p.N, n0, kbeg + BK, p.T);
   }
@@ -226,13 +164,13 @@ __global__ void __launch_bounds__(NT) wgrad_kernel(WgParams p) {
       bf16x8 a[2], b[2];
       // wave rows wm*64 .. +63 lie in image (wm >> 1), columns (wm & 1) * 64
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = trfrag(L + (wm >> 1) * IMG, (wm & 1) * 64 + 32 * i, s, lane);
+      for (int i = 0; i < 2; ++i) a[i] = trfrag<bf16x8>(L + (wm >> 1) * IMG, (wm & 1) * 64 + 32 * i, s, lane);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = trfrag(L + 2 * IMG, wn * 64 + 32 * j, s, lane);
+      for (int j = 0; j < 2; ++j) b[j] = trfrag<bf16x8>(L + 2 * IMG, wn * 64 + 32 * j, s, lane);
       if (s == 0) {  // tile t+1 (registers) -> the other buffer; tile t+2 -> registers
-        if (do_bias) ta.template store<true>(Ln, kbeg + (t + 1) * BK, kend, cs);
-        else ta.template store<false>(Ln, kbeg + (t + 1) * BK, kend, dummy);
-        tb.template store<false>(Ln + 2 * IMG, kbeg + (t + 1) * BK, kend, dummy);
+        if (do_bias) ta.template store<true, Bf16Ops>(Ln, kbeg + (t + 1) * BK, kend, true, cs);
+        else ta.template store<false, Bf16Ops>(Ln, kbeg + (t + 1) * BK, kend, false, dummy);
+        tb.template store<false, Bf16Ops>(Ln + 2 * IMG, kbeg + (t + 1) * BK, kend, false, dummy);
         ta.load(p.A, p.lda, p.M, m0, kbeg + (t + 2) * BK, p.T);
         tb.load(p.B, p.ldb, p.N, n0, kbeg + (t + 2) * BK, p.T);
       }
@@ -245,11 +183,6 @@ __global__ void __launch_bounds__(NT) wgrad_kernel(WgParams p) {
   }
 
   wgrad_finish(p, acc, cs, smem, do_bias, split, p.bparts > 1 ? tn : 0, m0, n0, wm, wn, lane);
-}
-
-__device__ __forceinline__ void glds16(const void* src, u16* lds_block) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_block, 16, 0, 0);
 }
 
 // one K-step (64 tokens at k0) -> stage st = [A cols m0..+127 | A cols m0+128..+255 | B cols n0..+127],
@@ -269,55 +202,13 @@ __device__ __forceinline__ void wgrad_issue(const WgParams& p, u16* st, int m0, 
   }
 }
 
-// The DMA loop reads its fragments with inline-asm ds_read_b64_tr_b16: the compiler's wait pass
-// puts an `s_waitcnt vmcnt(0)` (every LDS-DMA in flight, K-step t+2 included) in front of each
-// __builtin_amdgcn_ds_read_tr16_b64 it cannot tell apart from the DMA stores, which serialises the
-// ring. The asm reads are invisible to that pass, so their lgkmcnt waits are explicit (lgkm_wait):
-// LDS returns in order, and the fragments are "+v" operands of the wait, so no MFMA moves above it.
-__device__ __forceinline__ s16x4 ds_tr16_asm(const u16* p) {
-  const unsigned a = (unsigned)(size_t)(const __attribute__((address_space(3))) u16*)p;
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(a));
-  return v;
-}
-
-// the 8 half-fragments of one 16-deep substep: A (2 x lo/hi) then B (2 x lo/hi), as trfrag reads them
-__device__ __forceinline__ void read_substep(const u16* L, int wm, int wn, int s, int lane, s16x4 (&f)[8]) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
-  const int k = 16 * s + 8 * (g >> 1) + q;
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    const u16* P = x < 2 ? L + (wm >> 1) * IMG : L + 2 * IMG;
-    const int c0 = x < 2 ? (wm & 1) * 64 + 32 * x : wn * 64 + 32 * (x - 2);
-    const int col = c0 + 16 * (g & 1) + 4 * pp;
-    f[2 * x] = ds_tr16_asm(P + km_off(k, col >> 3) + (col & 7));
-    f[2 * x + 1] = ds_tr16_asm(P + km_off(k + 4, col >> 3) + (col & 7));
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void lgkm_wait(s16x4 (&f)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(%8)"
-               : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7])
-               : "n"(N));
-}
-
-__device__ __forceinline__ bf16x8 cat(s16x4 lo, s16x4 hi) {
-  return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
 template <bool BIAS>
 __global__ void __launch_bounds__(NT) wgrad_dma_kernel(WgParams p) {
   constexpr int BUF = 3 * IMG;  // u16 per stage: A two 128-col images, B one
   __shared__ __attribute__((aligned(16))) u16 smem[3 * BUF];
   const int ntiles = p.tiles_m * p.tiles_n;
   const int nwg = ntiles * p.splits;
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int split = wg / ntiles, tile = wg % ntiles;
   const int tm = p.nfast ? tile / p.tiles_n : tile % p.tiles_m, tn = p.nfast ? tile % p.tiles_n : tile / p.tiles_m;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -361,8 +252,8 @@ __global__ void __launch_bounds__(NT) wgrad_dma_kernel(WgParams p) {
       } else {
         lgkm_wait<0>(fr[s & 1]);
       }
-      const bf16x8 a[2] = {cat(fr[s & 1][0], fr[s & 1][1]), cat(fr[s & 1][2], fr[s & 1][3])};
-      const bf16x8 b[2] = {cat(fr[s & 1][4], fr[s & 1][5]), cat(fr[s & 1][6], fr[s & 1][7])};
+      const bf16x8 a[2] = {cat<bf16x8>(fr[s & 1][0], fr[s & 1][1]), cat<bf16x8>(fr[s & 1][2], fr[s & 1][3])};
+      const bf16x8 b[2] = {cat<bf16x8>(fr[s & 1][4], fr[s & 1][5]), cat<bf16x8>(fr[s & 1][6], fr[s & 1][7])};
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll

@@ -20,7 +20,8 @@
 //                     a torch inf-norm, the producing GEMM's per-wave maxima or the head's per-block bounds)
 //   x2_gemm_kernel    C[M][N] = A'[M][K'] . op(B') : BL = 0 "NT" (B [N][K], forward), BL = 1 "NN" (B [K][N],
 //                     input gradient); 256 x 256 tile, 8 waves of 128 x 64 (v_mfma_f32_16x16x32_f16),
-//                     K-step 64 by LDS-DMA into 2 x 64 KiB stages (gemm_bf16.hip's 2-phase loop and swizzles);
+//                     K-step 64 by LDS-DMA into 2 x 64 KiB stages (the 2-phase loop of gemm_bf16.hip; the swizzles
+//                     and the DMA / transposed-read primitives are mma_prims.h's);
 //                     fp32 epilogue through LDS (16-B row stores): bias, ReLU, ReLU mask of the layer input,
 //                     per-wave max |C| for the consumer's split
 //   x2_wgrad_kernel   gW[N][K] += sum_m dz[m][n] x[m][k] (both operands k-major, hardware transpose reads),
@@ -28,8 +29,8 @@
 //                     workgroups (one grid wave), fp32 slabs reduced in a fixed order (deterministic) with the
 //                     bias gradient (column sums of dz: hi in segment 0, lo in segment 2). Two main loops:
 //                     x2_wgrad_dma_kernel (T % 64 == 0, default) fills a 3-stage LDS ring by LDS-DMA with two
-//                     K-steps in flight (gemm_bf16_wgrad.hip's wgrad_dma_kernel); x2_wgrad_kernel stages
-//                     through VGPRs (any T; SDML_WGRAD_DMA=0). 588 -> 502 us at 65536 x 1024 x 1024
+//                     K-steps in flight; x2_wgrad_kernel stages through VGPRs (any T; knob WGRAD_DMA = 0). Tile,
+//                     images and fragment reads of both: wgrad_tiles.h. 588 -> 502 us at 65536 x 1024 x 1024
 //                     (profiles/r3_wgrad_dma_vs_staged.json)
 #include <hip/hip_runtime.h>
 
@@ -40,18 +41,10 @@
 
 #include "kernels.h"
 #include "tile_order.h"
+#include "wgrad_tiles.h"
 
 namespace sdml {
 namespace {
-
-typedef unsigned short u16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef u16 u16x4 __attribute__((ext_vector_type(4)));
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
 
 // exponent E with |v| < 2^E for finite v >= 0, clamped so 2^(14 - E) and 2^(E - 14) stay normal floats
 __device__ __forceinline__ int bound_exp(float v) {
@@ -123,14 +116,6 @@ struct X2Gemm {
   int group_m;  // tile order (tile_order.h): 0 = M fastest; g > 0 = groups of g m-tiles x every n-tile
 };
 
-__device__ __forceinline__ void glds16(const void* src, unsigned char* lds_block) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_block, 16, 0, 0);
-}
-
-__device__ __forceinline__ int rk_swz(int r) { return (r >> 1) & 7; }                          // [rows][64]
-__device__ __forceinline__ int kn_swz(int r) { return ((r & 3) | ((r >> 1) & 4)) << 1; }       // [64][256]
-
 // K-step t of the extended K axis: plane pair (t / nk) of {(hi, hi), (hi, lo), (lo, hi)}, k0 in the segment
 template <int BL>
 __device__ __forceinline__ void issue_stage(const X2Gemm& p, unsigned char* st, int m0, int n0, int t, int nk,
@@ -164,9 +149,6 @@ __device__ __forceinline__ void issue_stage(const X2Gemm& p, unsigned char* st, 
 }
 
 __device__ __forceinline__ f16x8 ld_b128(const unsigned char* p) { return *reinterpret_cast<const f16x8*>(p); }
-__device__ __forceinline__ s16x4 ds_tr16(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
 
 // fp32 epilogue: each wave's 128 x 64 tile in two 64-row halves through a wave-private [64][64] fp32 LDS
 // image (16-B chunk c of row r at c ^ (((r >> 2) & 3) << 2): conflict-free writes from the MFMA layout
@@ -233,11 +215,7 @@ template <int BL, int EPI>
 __global__ void __launch_bounds__(GT) x2_gemm_kernel(X2Gemm p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM];
   const int nwg = p.tiles_m * p.tiles_n;
-  int wg = blockIdx.x;
-  if (nwg >= 16) {  // XCD-aware bijective remap: blocks sharing an XCD get consecutive tile ids
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + wg / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   int tm, tn;
   tile_of(wg, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
   const int m0 = tm * TM, n0 = tn * TN;
@@ -348,11 +326,7 @@ template <int EPI>
 __global__ void __launch_bounds__(GT) x2_gemm_nt4_kernel(X2Gemm p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[NSLOT * HT];  // the epilogue reuses it
   const int nwg = p.tiles_m * p.tiles_n;
-  int wg = blockIdx.x;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + wg / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   int tm, tn;
   tile_of(wg, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
   const int m0 = tm * TM, n0 = tn * TN;
@@ -499,12 +473,9 @@ __global__ void __launch_bounds__(256) x2_split_t_kernel(const float* __restrict
 
 // ================================================================================================
 // weight gradient: gW[M][N] += sum_t A[t][m] B[t][n] with A = dz planes [T][lda], B = x planes [T][ldb]
-// (gemm_bf16_wgrad.hip's geometry: 256 x 128 tile, 8 waves of 64 x 64, 32x32x16 MFMAs, register-staged
-// k-major images read by ds_read_b64_tr_b16). The 3 plane pairs form one extended K axis of 3 ceil(T / 64)
+// (wgrad_tiles.h's geometry, images and fragment reads: 256 x 128 tile, 8 waves of 64 x 64, 32x32x16 MFMAs, k-major
+// images read by ds_read_b64_tr_b16). The 3 plane pairs form one extended K axis of 3 ceil(T / 64)
 // K-steps; split s covers K-steps [s kps, (s + 1) kps), and every tile of one split runs on one XCD.
-constexpr int WNT = 512, WBM = 256, WBN = 128, WBK = 64;
-constexpr int IMG = WBK * 128;  // u16 per 128-column image
-
 struct X2Wg {
   const u16* A;  // dz planes
   const u16* B;  // x planes
@@ -516,56 +487,6 @@ struct X2Wg {
   int splits;
   int tiles_m, tiles_n;
   int bparts;  // bias partials per split (x2_wgrad_dma_kernel: tiles_n, block tn sums K-steps e % tiles_n == tn)
-};
-
-__device__ __forceinline__ int km_off(int k, int ch) { return k * 128 + 8 * (ch ^ (((k & 3) << 2) | ((k >> 2) & 3))); }
-
-__device__ __forceinline__ f16x8 trfrag(const u16* P, int c0, int s, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
-  const int k = 16 * s + 8 * (g >> 1) + q;
-  const int col = c0 + 16 * (g & 1) + 4 * pp;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(P + km_off(k, col >> 3) + (col & 7)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(P + km_off(k + 4, col >> 3) + (col & 7)));
-  return __builtin_bit_cast(f16x8, s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-}
-
-__device__ __forceinline__ float h2f(u16 v) { return static_cast<float>(__builtin_bit_cast(_Float16, v)); }
-
-template <int COLS>
-struct KmTile {
-  static constexpr int CPR = COLS / 8;      // chunks per k-row
-  static constexpr int NV = WBK * CPR / WNT;  // chunks per thread
-  u16x8 v[NV];
-  // the K-step's rows k0 .. k0 + 63 of plane P (rows past T re-read row T - 1; zeroed in store)
-  __device__ __forceinline__ void load(const u16* __restrict__ P, int ld, int cols, int c0, int k0, int T) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int id = threadIdx.x + WNT * u;
-      const int k = min(k0 + id / CPR, T - 1);
-      const int c = min(c0 + 8 * (id % CPR), cols - 8);
-      v[u] = *reinterpret_cast<const u16x8*>(P + (size_t)k * ld + c);
-    }
-  }
-  // rows k0 + k >= T are stored as zeros; colsum[e] += the staged values when `sum`
-  template <bool ROWSUM>
-  __device__ __forceinline__ void store(u16* L, int k0, int T, bool sum, float (&colsum)[8]) const {
-    const u16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int id = threadIdx.x + WNT * u;
-      const int k = id / CPR, ch = id % CPR;
-      const u16x8 val = (k0 + k < T) ? v[u] : z;
-      *reinterpret_cast<u16x8*>(L + (ch >> 4) * IMG + km_off(k, ch & 15)) = val;
-      if constexpr (ROWSUM) {
-        if (sum) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) colsum[e] += h2f(val[e]);
-        }
-      }
-    }
-  }
 };
 
 // bias partials (16 row groups -> LDS -> 256 column sums) and the partial tile -> slab; smem must be free
@@ -612,12 +533,7 @@ __global__ void __launch_bounds__(WNT) x2_wgrad_kernel(X2Wg p) {
   __shared__ __attribute__((aligned(16))) u16 smem[2 * BUF];
   const int ntiles = p.tiles_m * p.tiles_n;
   const int nwg = ntiles * p.splits;
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (nwg >= 16) {  // XCD-aware: the tiles of one split (same token range) share an XCD's L2
-    const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);  // the tiles of one split (same token range) share an XCD's L2
   const int split = wg / ntiles, tile = wg % ntiles;
   const int tm = tile % p.tiles_m, tn = tile / p.tiles_m;
   const int m0 = tm * WBM, n0 = tn * WBN;
@@ -644,9 +560,9 @@ __global__ void __launch_bounds__(WNT) x2_wgrad_kernel(X2Wg p) {
   };
   auto store = [&](u16* L, int e) {  // bias: dz hi (pair 0) + dz lo (pair 2)
     const int seg = seg_of(e), k0 = (e - seg * p.nks) * WBK;
-    if (do_bias) ta.template store<true>(L, k0, p.T, seg != 1, cs);
-    else ta.template store<false>(L, k0, p.T, false, cs);
-    tb.template store<false>(L + 2 * IMG, k0, p.T, false, cs);
+    if (do_bias) ta.template store<true, F16Ops>(L, k0, p.T, seg != 1, cs);
+    else ta.template store<false, F16Ops>(L, k0, p.T, false, cs);
+    tb.template store<false, F16Ops>(L + 2 * IMG, k0, p.T, false, cs);
   };
   const int nk = max(0, eend - ebeg);
   if (nk > 0) {
@@ -662,9 +578,9 @@ __global__ void __launch_bounds__(WNT) x2_wgrad_kernel(X2Wg p) {
     for (int s = 0; s < WBK / 16; ++s) {
       f16x8 a[2], b[2];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = trfrag(L + (wm >> 1) * IMG, (wm & 1) * 64 + 32 * i, s, lane);
+      for (int i = 0; i < 2; ++i) a[i] = trfrag<f16x8>(L + (wm >> 1) * IMG, (wm & 1) * 64 + 32 * i, s, lane);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = trfrag(L + 2 * IMG, wn * 64 + 32 * j, s, lane);
+      for (int j = 0; j < 2; ++j) b[j] = trfrag<f16x8>(L + 2 * IMG, wn * 64 + 32 * j, s, lane);
       if (s == 0 && t + 1 < nk) {  // K-step t+1 (registers) -> the other buffer; K-step t+2 -> registers
         store(Ln, ebeg + t + 1);
         if (t + 2 < nk) load(ebeg + t + 2);
@@ -680,10 +596,9 @@ __global__ void __launch_bounds__(WNT) x2_wgrad_kernel(X2Wg p) {
   x2w_finish(p, acc, cs, smem, do_bias, split, 0, m0, n0, wm, wn, lane);
 }
 
-// ---- LDS-DMA form of the weight gradient (T % 64 == 0; gemm_bf16_wgrad.hip's wgrad_dma_kernel with the
-// plane pair chosen per K-step): 3-stage ring of [A 2 x 128 cols | B 128 cols] images filled by
-// global_load_lds (the km_off swizzle on the per-lane source address), two K-steps in flight, one
-// counted vmcnt(6) + barrier per K-step, fragments by inline-asm transposed reads (see x2w_tr16).
+// ---- LDS-DMA form of the weight gradient (T % 64 == 0): 3-stage ring of [A 2 x 128 cols | B 128 cols] images filled
+// by glds16 (the km_off swizzle on the per-lane source address; gemm_bf16_wgrad.hip's wgrad_issue with the plane pair
+// chosen per K-step), two K-steps in flight, one counted vmcnt(6) + barrier per K-step, fragments by read_substep
 __device__ __forceinline__ void x2w_issue(const X2Wg& p, u16* st, int m0, int n0, int e, int wave, int lane) {
   const int seg = e / p.nks, k0 = (e - seg * p.nks) * WBK;
   const u16* A = p.A + (seg == 2 ? p.a_ps : 0);
@@ -695,42 +610,8 @@ __device__ __forceinline__ void x2w_issue(const X2Wg& p, u16* st, int m0, int n0
     const int c = (lane & 15) ^ (((r & 3) << 2) | ((r >> 2) & 3));
     const u16* src = img < 2 ? A + (size_t)(k0 + r) * p.lda + min(m0 + 128 * img + 8 * c, p.M - 8)
                              : B + (size_t)(k0 + r) * p.ldb + min(n0 + 8 * c, p.N - 8);
-    glds16(src, reinterpret_cast<unsigned char*>(st + q * 512));
+    glds16(src, st + q * 512);
   }
-}
-
-// inline-asm ds_read_b64_tr_b16: the builtin makes the compiler wait for every LDS-DMA in flight
-// (vmcnt(0)) before each read; these are invisible to its wait pass, so lgkmcnt is waited explicitly
-// with the fragments as "+v" operands (no MFMA can move above the wait)
-__device__ __forceinline__ s16x4 x2w_tr16(const u16* p) {
-  const unsigned a = (unsigned)(size_t)(const __attribute__((address_space(3))) u16*)p;
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(a));
-  return v;
-}
-
-__device__ __forceinline__ void x2w_read(const u16* L, int wm, int wn, int s, int lane, s16x4 (&f)[8]) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
-  const int k = 16 * s + 8 * (g >> 1) + q;
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    const u16* P = x < 2 ? L + (wm >> 1) * IMG : L + 2 * IMG;
-    const int c0 = x < 2 ? (wm & 1) * 64 + 32 * x : wn * 64 + 32 * (x - 2);
-    const int col = c0 + 16 * (g & 1) + 4 * pp;
-    f[2 * x] = x2w_tr16(P + km_off(k, col >> 3) + (col & 7));
-    f[2 * x + 1] = x2w_tr16(P + km_off(k + 4, col >> 3) + (col & 7));
-  }
-}
-
-template <int N>
-__device__ __forceinline__ void x2w_wait(s16x4 (&f)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(%8)"
-               : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7])
-               : "n"(N));
-}
-
-__device__ __forceinline__ f16x8 x2w_cat(s16x4 lo, s16x4 hi) {
-  return __builtin_bit_cast(f16x8, s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
 }
 
 template <bool BIAS>
@@ -739,12 +620,7 @@ __global__ void __launch_bounds__(WNT) x2_wgrad_dma_kernel(X2Wg p) {
   __shared__ __attribute__((aligned(16))) u16 smem[3 * BUF];
   const int ntiles = p.tiles_m * p.tiles_n;
   const int nwg = ntiles * p.splits;
-  const int orig = blockIdx.x;
-  int wg = orig;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int split = wg / ntiles, tile = wg % ntiles;
   const int tm = tile % p.tiles_m, tn = tile / p.tiles_m;
   const int m0 = tm * WBM, n0 = tn * WBN;
@@ -773,17 +649,17 @@ __global__ void __launch_bounds__(WNT) x2_wgrad_dma_kernel(X2Wg p) {
     const u16* L = smem + (t % 3) * BUF;
     x2w_issue(p, smem + ((t + 2) % 3) * BUF, m0, n0, estep(t + 2), wave, lane);
     s16x4 fr[2][8];
-    x2w_read(L, wm, wn, 0, lane, fr[0]);
+    read_substep(L, wm, wn, 0, lane, fr[0]);
 #pragma unroll
     for (int s = 0; s < WBK / 16; ++s) {
       if (s + 1 < WBK / 16) {
-        x2w_read(L, wm, wn, s + 1, lane, fr[(s + 1) & 1]);
-        x2w_wait<8>(fr[s & 1]);
+        read_substep(L, wm, wn, s + 1, lane, fr[(s + 1) & 1]);
+        lgkm_wait<8>(fr[s & 1]);
       } else {
-        x2w_wait<0>(fr[s & 1]);
+        lgkm_wait<0>(fr[s & 1]);
       }
-      const f16x8 a[2] = {x2w_cat(fr[s & 1][0], fr[s & 1][1]), x2w_cat(fr[s & 1][2], fr[s & 1][3])};
-      const f16x8 b[2] = {x2w_cat(fr[s & 1][4], fr[s & 1][5]), x2w_cat(fr[s & 1][6], fr[s & 1][7])};
+      const f16x8 a[2] = {cat<f16x8>(fr[s & 1][0], fr[s & 1][1]), cat<f16x8>(fr[s & 1][2], fr[s & 1][3])};
+      const f16x8 b[2] = {cat<f16x8>(fr[s & 1][4], fr[s & 1][5]), cat<f16x8>(fr[s & 1][6], fr[s & 1][7])};
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -796,7 +672,7 @@ __global__ void __launch_bounds__(WNT) x2_wgrad_dma_kernel(X2Wg p) {
       for (int u = 0; u < 4; ++u) {
         const u16x8 v = *reinterpret_cast<const u16x8*>(L + (bch >> 4) * IMG + km_off(brg + 16 * u, bch & 15));
 #pragma unroll
-        for (int x = 0; x < 8; ++x) cs[x] += h2f(v[x]);
+        for (int x = 0; x < 8; ++x) cs[x] += F16Ops::widen(v[x]);
       }
     }
     asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");

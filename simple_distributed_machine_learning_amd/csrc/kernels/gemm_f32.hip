@@ -28,6 +28,7 @@
 #include <string>
 
 #include "kernels.h"
+#include "tile_order.h"
 
 namespace sdml {
 namespace {
@@ -176,12 +177,7 @@ __global__ void __launch_bounds__(NTHR, 2) gemm_f32_kernel(KParams p) {
   // read those slices through its L2 instead of once per tile from HBM.
   const int ntiles = p.tiles_m * p.tiles_n;
   const int nwg = ntiles * gridDim.y;
-  int orig = blockIdx.y * gridDim.x + blockIdx.x;
-  int wg = orig;
-  if (nwg >= 16) {
-    int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, nwg);
   const int split = wg / ntiles, tile = wg % ntiles;
   const int tm = tile % p.tiles_m, tn = tile / p.tiles_m;
   const int m0 = tm * BM, n0 = tn * BN;

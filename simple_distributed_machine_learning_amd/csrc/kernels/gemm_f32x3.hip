@@ -39,17 +39,12 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "mma_prims.h"
+#include "tile_order.h"
 
 namespace sdml {
 namespace {
 
-typedef unsigned short u16;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-typedef u16 u16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -103,14 +98,7 @@ __device__ __forceinline__ void split3(const float (&x)[N], u16 (&h)[N], u16 (&m
 // ---- LDS images (offsets in u16 elements) ------------------------------------------------------
 // k-contiguous image [rows][32]: chunk ch (8 k) of row r
 __device__ __forceinline__ int kc_off(int r, int ch) { return r * BK + 8 * (ch ^ ((r >> 2) & 3)); }
-// k-major image [32][128]: 16-B chunk ch (8 rows) of k-row k
-__device__ __forceinline__ int km_off(int k, int ch) {
-  return k * 128 + 8 * (ch ^ (((k & 3) << 2) | ((k >> 2) & 3)));
-}
-
-__device__ __forceinline__ s16x4 ds_tr16(const u16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
+// k-major image [32][128]: 16-B chunk ch (8 rows) of k-row k at km_off(k, ch) (mma_prims.h)
 
 // A/B fragment of the 32-row sub-tile at r0, k-substep s (k = 16s + 8h + j), natural k order
 template <bool KM>
@@ -454,12 +442,7 @@ __global__ void __launch_bounds__(NT) gemm_x3_kernel(X3Params p) {
   // the same K-slice of the shared operand read it through one L2.
   const int ntiles = p.tiles_m * p.tiles_n;
   const int nwg = ntiles * gridDim.y;
-  const int orig = blockIdx.y * gridDim.x + blockIdx.x;
-  int wg = orig;
-  if (nwg >= 16) {
-    const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  }
+  const int wg = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, nwg);
   const int split = wg / ntiles, tile = wg % ntiles;
   const int tm = tile % p.tiles_m, tn = tile / p.tiles_m;
   const int m0 = tm * BM, n0 = tn * BN;

@@ -43,6 +43,7 @@
 #include "head_tile.h"
 #include "lds_dma.h"
 #include "kernels.h"
+#include "mma_prims.h"
 #include "sgd_rule.h"
 #include "wave_ops.h"
 #include "u8_planes.h"
@@ -50,13 +51,7 @@
 namespace sdml {
 namespace {
 
-typedef unsigned short u16;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int FBN = 128;                      // columns per block
@@ -93,11 +88,6 @@ struct Geo {
 // logical chunk) hits 16 distinct bank groups
 __device__ __forceinline__ int xpos(int r, int c) { return c ^ (XCH == 2 ? (r >> 3) & 1 : (r >> 2) & 3); }
 __device__ __forceinline__ int wpos(int r, int c) { return c ^ (WCH == 4 ? (r >> 2) & 3 : (r >> 1) & 7); }
-
-__device__ __forceinline__ void glds16(const void* src, unsigned char* lds_block) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_block, 16, 0, 0);
-}
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {

@@ -8,6 +8,17 @@
 
 namespace sdml {
 
+// XCD-aware bijective remap of a launch's block ids (every tiled kernel calls it first). The hardware deals blocks
+// round-robin to the 8 XCDs (block id % 8); this gives the blocks that share an XCD consecutive logical ids, so tiles
+// that share an operand panel (or one split's token range) meet in one XCD's L2. Grids under 16 blocks are left alone.
+__device__ __forceinline__ int xcd_remap(int wg, int nwg) {
+  if (nwg >= 16) {
+    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + wg / 8;
+  }
+  return wg;
+}
+
 __device__ __forceinline__ void tile_of(int wg, int tiles_m, int tiles_n, int gm, int& tm, int& tn) {
   if (gm <= 0) {
     tm = wg % tiles_m;
