@@ -1,0 +1,161 @@
+// Single-token (decode) attention against a KV cache, bf16, head width 64 (models/gpt2.py decode_step).
+//
+// For each (sample b, head h) the new token's q, k, v come from its fused projection qkv [B][3C]; the cache holds
+// lens[b] earlier keys. The kernel writes the new k and v rows to cache index lens[b] and returns
+//   softmax(q . K[0..lens[b]]^T * scale) . V[0..lens[b]]        (lens[b] + 1 keys, the new one included)
+//
+// Memory-bound: every K and V row is read once, so the rows go straight to VGPRs in 16-B pieces (a row is 8 lanes, a
+// wave has 8 rows in flight per load and 8 + 8 loads outstanding); the products run on the VALU in fp32, which at one
+// query per head is a few percent of the time of the loads. No LDS, no MFMA.
+//
+// Parallelism: B * H is far below the chip's wave slots, so the key range is cut into chunks of kAttnDecodeChunk keys
+// (a compile-time constant, not derived from the batch), one wave each; a second launch combines the chunks'
+// (max, sum, partial O) in chunk order. No atomics. A sample's result depends on its own row of qkv, its own cache
+// rows and lens[b] only: the same bits on every run, in any batch.
+//
+// Keys past lens[b] never reach the result: their loads are redirected to the new token's own row (so nothing is read
+// from cache rows >= lens[b], which may hold anything), their scores and probabilities are selected away, not
+// multiplied by zero. The chunk that contains index lens[b] owns the cache write, and takes that key from qkv, so no
+// wave reads a row that another wave writes.
+//
+// Rounding: scores, exp2, sums and the combine are fp32; the output is rounded to bf16 once.
+#include <hip/hip_bf16.h>
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+#include "wave_ops.h"
+
+namespace sdml {
+namespace {
+
+typedef unsigned short u16;
+typedef u16 u16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int CH = kAttnDecodeChunk;  // keys per wave
+constexpr int RPL = CH / 8;           // rows per lane (8 lanes hold one row)
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr int ROR8 = 0x128;  // DPP row_ror:8: lane i <- lane i ^ 8 inside a row of 16
+
+__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
+__device__ __forceinline__ u16 f2bf(float f) {
+  __hip_bfloat16 h = __float2bfloat16(f);
+  return *reinterpret_cast<u16*>(&h);
+}
+
+// sum / max over the 8 row groups of a wave (lane bits 3..5); lanes that differ only in those bits hold the addends
+__device__ __forceinline__ float sum_groups(float x) { return wv::sum_rows(x + wv::dpp<ROR8>(x)); }
+__device__ __forceinline__ float max_groups(float x) { return wv::max_rows(fmaxf(x, wv::dpp<ROR8>(x))); }
+
+// grid (chunks, H, B), one wave per block. Lane l: piece l & 7 (channels 8 (l & 7) ..), row group l >> 3; its keys
+// are chunk * CH + 8 i + (l >> 3), i = 0 .. RPL - 1.
+__global__ void __launch_bounds__(64) attn_decode_chunk_kernel(AttnDecodeArgs p) {
+  const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
+  const int len = p.lens[b];
+  if (len < 0 || len >= p.Smax) return;  // (refused by the host API; never index outside the cache)
+  if (c * CH > len) return;
+  const int pc = lane & 7, rg = lane >> 3;
+  const int C = p.H * 64;
+  const u16* qrow = static_cast<const u16*>(p.qkv) + (int64_t)b * p.ldq + h * 64 + 8 * pc;
+  const u16* knew = qrow + C;
+  const u16* vnew = qrow + 2 * C;
+  const int64_t base = (int64_t)b * p.sb + (int64_t)h * p.sh + 8 * pc;
+  u16* kc = static_cast<u16*>(p.k_cache) + base;
+  u16* vc = static_cast<u16*>(p.v_cache) + base;
+
+  u16x8 kv[RPL], vv[RPL];
+#pragma unroll
+  for (int i = 0; i < RPL; ++i) {
+    const int j = c * CH + 8 * i + rg;
+    const bool cached = j < len;
+    kv[i] = *reinterpret_cast<const u16x8*>(cached ? kc + (int64_t)j * p.ss : knew);
+  }
+#pragma unroll
+  for (int i = 0; i < RPL; ++i) {
+    const int j = c * CH + 8 * i + rg;
+    const bool cached = j < len;
+    vv[i] = *reinterpret_cast<const u16x8*>(cached ? vc + (int64_t)j * p.ss : vnew);
+  }
+  const u16x8 qv = *reinterpret_cast<const u16x8*>(qrow);
+  float q[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) q[e] = bf2f(qv[e]);
+
+  const float sl2 = p.scale * kLog2e;
+  float s[RPL];
+  float m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < RPL; ++i) {
+    const int j = c * CH + 8 * i + rg;
+    if (j == len) {  // the new token's row: bit for bit from qkv
+      *reinterpret_cast<u16x8*>(kc + (int64_t)j * p.ss) = kv[i];
+      *reinterpret_cast<u16x8*>(vc + (int64_t)j * p.ss) = vv[i];
+    }
+    float a = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a = fmaf(q[e], bf2f(kv[i][e]), a);
+    a += wv::dpp<wv::XOR1>(a);
+    a += wv::dpp<wv::XOR2>(a);
+    a += wv::dpp<wv::HALF_MIRROR>(a);  // the row's 8 lanes hold the same sum
+    s[i] = j <= len ? a * sl2 : -INFINITY;
+    m = fmaxf(m, s[i]);
+  }
+  m = max_groups(m);  // finite: key c * CH <= len is in this chunk
+
+  float l = 0.f, o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < RPL; ++i) {
+    const int j = c * CH + 8 * i + rg;
+    const float pr = j <= len ? __builtin_amdgcn_exp2f(s[i] - m) : 0.f;
+    l += pr;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = fmaf(pr, bf2f(vv[i][e]), o[e]);
+  }
+  l = sum_groups(l);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = sum_groups(o[e]);
+
+  const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks + c;
+  if (lane < 8) {
+    f32x4* dst = reinterpret_cast<f32x4*>(p.ws_o + slot * 64 + 8 * pc);
+    dst[0] = f32x4{o[0], o[1], o[2], o[3]};
+    dst[1] = f32x4{o[4], o[5], o[6], o[7]};
+  }
+  if (lane == 0) {
+    p.ws_ml[slot * 2] = m;
+    p.ws_ml[slot * 2 + 1] = l;
+  }
+}
+
+// grid (H, B), one wave per block, lane = channel: the chunks of one (b, h) in chunk order
+__global__ void __launch_bounds__(64) attn_decode_combine_kernel(AttnDecodeArgs p) {
+  const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const int len = p.lens[b];
+  if (len < 0 || len >= p.Smax) return;
+  const int nc = len / CH + 1;  // <= max_chunks: the host checked lens[b] + 1 <= n_keys
+  if (nc > p.max_chunks) return;
+  const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks;
+  float M = -INFINITY;
+  for (int c = 0; c < nc; ++c) M = fmaxf(M, p.ws_ml[(slot + c) * 2]);
+  float L = 0.f, O = 0.f;
+  for (int c = 0; c < nc; ++c) {
+    const float w = __builtin_amdgcn_exp2f(p.ws_ml[(slot + c) * 2] - M);
+    L = fmaf(p.ws_ml[(slot + c) * 2 + 1], w, L);
+    O = fmaf(p.ws_o[(slot + c) * 64 + lane], w, O);
+  }
+  static_cast<u16*>(p.out)[(int64_t)b * p.H * 64 + h * 64 + lane] = f2bf(O / L);
+}
+
+}  // namespace
+
+int attention_decode_chunks(int n_keys) { return (n_keys + CH - 1) / CH; }
+
+void attention_decode_bf16(const AttnDecodeArgs& a, hipStream_t stream) {
+  if (a.B <= 0 || a.H <= 0 || a.max_chunks <= 0) return;
+  hipLaunchKernelGGL(attn_decode_chunk_kernel, dim3(a.max_chunks, a.H, a.B), dim3(64), 0, stream, a);
+  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(a.H, a.B), dim3(64), 0, stream, a);
+}
+
+}  // namespace sdml

@@ -16,6 +16,8 @@
 namespace sdml {
 
 enum DropSite : unsigned { DROP_SITE_EMBD = 1, DROP_SITE_ATTN = 2, DROP_SITE_RESID_ATTN = 3, DROP_SITE_RESID_MLP = 4 };
+// the sampler's noise (sample.hip) draws from the same hash: layer 0, head 0, a = position, b4 = vocabulary id
+constexpr unsigned DROP_SITE_SAMPLE = 5;
 
 __host__ __device__ __forceinline__ unsigned long long drop_splitmix64(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;

@@ -493,6 +493,45 @@ void attention_fwd_bf16(const AttnShape& s, hipStream_t stream);
 void attention_set_fwd_kb(int kb);  // tuning: keys per forward tile (0 = default, 64, 128)
 void attention_bwd_bf16(const AttnShape& s, hipStream_t stream);
 
+// ---- generation: decode attention, decode projections, sampler (attention_decode.hip, linear_decode.hip,
+// sample.hip) -------------------------------------------------------------------------------
+// One new token per sample against a KV cache (bf16, head width 64). qkv [B][ldq] holds the token's fused
+// projection (q | k | v, C = 64 H each); k_cache / v_cache share one strided layout [b][s][h][64] (strides sb, ss,
+// sh in elements, multiples of 8; channels contiguous); lens [B] int32 on the device = keys already cached. Writes
+// the new k, v to cache row lens[b] and out [B][C] = softmax(q K[0..lens[b]]^T scale) V[0..lens[b]]. lens is not
+// changed. The host guarantees lens[b] + 1 <= n_keys <= Smax; max_chunks = attention_decode_chunks(n_keys).
+// ws_ml: [B][H][max_chunks][2] fp32, ws_o: [B][H][max_chunks][64] fp32.
+constexpr int kAttnDecodeChunk = 64;  // keys per wave: a compile-time constant, not derived from the batch
+struct AttnDecodeArgs {
+  const void* qkv = nullptr;
+  void *k_cache = nullptr, *v_cache = nullptr, *out = nullptr;
+  const int* lens = nullptr;
+  float *ws_ml = nullptr, *ws_o = nullptr;
+  int B = 0, H = 0, Smax = 0, max_chunks = 0;
+  long ldq = 0, sb = 0, ss = 0, sh = 0;
+  float scale = 1.f;
+};
+int attention_decode_chunks(int n_keys);
+void attention_decode_bf16(const AttnDecodeArgs& a, hipStream_t stream);
+// y[M][N] = x[M][K] W[N][K]^T with epi EPI_STORE, EPI_BIAS or EPI_BIAS_GELU (bias [N] bf16); 1 <= M <=
+// kLinearDecodeMaxM, K % 64 == 0, N % 16 == 0, leading dimensions % 8 == 0, 16-B aligned operands, y contiguous.
+// ws: linear_decode_workspace_floats(M, N, K) fp32 (0: none). Deterministic; a row's bits do not depend on M.
+constexpr int kLinearDecodeMaxM = 64;
+constexpr int kLinearDecodeMinBlocks = 256;  // workgroups a shape is split into where K allows (the CU count)
+bool linear_decode_supported(int M, int N, int K, int ldx, int ldw);
+int linear_decode_splits(int N, int K);
+size_t linear_decode_workspace_floats(int M, int N, int K);
+void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y, float* ws, int M, int N, int K,
+                        int ldx, int ldw, int epi, hipStream_t stream);
+// out[r] (int64) = the token of row r of bf16 logits [rows][ld] among columns < vocab: inv_temp == 0 greedy, else
+// Gumbel-max at 1 / T = inv_temp over the top_k candidates (top_k <= 0 or >= vocab: all), noise keyed by
+// (seed, sample0 + r, pos[r], token) (sample.hip). pos: int32 [rows] on the device.
+void sample_logits_bf16(const void* logits, int rows, int ld, int vocab, float inv_temp, int top_k,
+                        unsigned long long seed, unsigned sample0, const int* pos, int64_t* out, hipStream_t stream);
+// out[r] = bf16(wte[tok[r]] + wpe[pos[r]])  (C % 4 == 0; wte [V][C], wpe [P][C]; pos int32 on the device)
+void embedding_at_bf16(const int64_t* tok, const int* pos, const void* wte, const void* wpe, void* out, int rows, int C,
+                       int V, int P, hipStream_t stream);
+
 // ---- reference CNN (MNIST), fp32, one launch per stage pass (ref_cnn.hip) ------------------
 // Dropout masks: keep iff u(seed_eff, sample0 + n, unit) >= p, scale 1/(1-p) (drop == false: off),
 // seed_eff = seed + 0x9E3779B97F4A7C15 * (*ctr) (ctr: optional device step counter).

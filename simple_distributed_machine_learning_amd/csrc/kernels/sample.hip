@@ -1,0 +1,188 @@
+// Generation's two small kernels (parallel/generate.py): the on-device sampler and the decode-time embedding.
+//
+// sample_logits: one workgroup per row of bf16 logits [B][ld]; only columns < vocab take part (the lm_head's padded
+// columns hold zeros and must never win).
+//   * temperature == 0 (inv_temp == 0 here): greedy, argmax with the lowest index on ties.
+//   * top_k in 1 .. vocab - 1: the candidates are the tokens whose logit is >= the k-th largest logit VALUE (ties at
+//     the boundary are all kept). bf16 has 65,536 bit patterns: two 256-bin histogram passes (high byte, then low
+//     byte inside the boundary bin) over an order-preserving 16-bit key find that value exactly. -0 is keyed as +0.
+//   * temperature > 0: Gumbel-max over the candidates, token = argmax_v (l_v * (1 / T) + g_v), lowest index on ties,
+//     g_v = -log(-log u_v) with the accurate logf (-log u reaches 1.2e-7, where an absolute-error log is useless),
+//     u_v = ((word >> 9) + 0.5) * 2^-23: exact in fp32, inside [2^-24, 1 - 2^-24]. One fp32 multiply and one add (no
+//     contraction), so the torch twin (ops/reference.py) differs by the two logs' last ulps only.
+//   * The word is dropout_hash.h's counter hash at site DROP_SITE_SAMPLE, layer 0, head 0:
+//       rkey = drop_row_key(drop_site_key(seed, 5 << 16), sample0 + row, 0);  word = drop_word(rkey, position, v)
+//     with the vocabulary id in the b4 slot (one word per candidate) and position = the index of the token being
+//     drawn. No step counter: a token is a function of (seed, sample, position, logits) alone.
+//   NaN logits never win a comparison. Integer LDS atomics build the histograms; no float atomics anywhere.
+//
+// embedding_at: out[b] = bf16(wte[tok[b]] + wpe[pos[b]]) for one token per sample at a per-sample position read on
+// the device (the cache length), where embedding_fwd_bf16 hard-wires position = column.
+#include <hip/hip_bf16.h>
+#include <hip/hip_runtime.h>
+
+#include "dropout_hash.h"
+#include "kernels.h"
+
+namespace sdml {
+namespace {
+
+typedef unsigned short u16;
+typedef u16 u16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int ST = 1024;  // sampler threads per row
+
+__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
+__device__ __forceinline__ u16 f2bf(float f) {
+  __hip_bfloat16 h = __float2bfloat16(f);
+  return *reinterpret_cast<u16*>(&h);
+}
+
+// order-preserving 16-bit key of a bf16 bit pattern (larger value <-> larger key); -0 -> the key of +0
+__device__ __forceinline__ unsigned key16(u16 b) {
+  if (b == 0x8000u) b = 0;
+  return (b & 0x8000u) ? (unsigned)(u16)~b : (unsigned)b | 0x8000u;
+}
+__device__ __forceinline__ bool is_nan_bf16(u16 b) { return (b & 0x7FFFu) > 0x7F80u; }
+
+// better(a, b): does (sa, ia) beat (sb, ib)? larger score, then lower index; index < 0 = nothing yet
+__device__ __forceinline__ bool better(float sa, int ia, float sb, int ib) {
+  return ia >= 0 && (ib < 0 || sa > sb || (sa == sb && ia < ib));
+}
+
+struct SampleParams {
+  const u16* logits;
+  const int* pos;
+  int64_t* out;
+  int ld, vocab, top_k;
+  float inv_temp;  // 0: greedy
+  unsigned long long seed;
+  unsigned sample0;
+};
+
+__global__ void __launch_bounds__(ST) sample_logits_kernel(SampleParams p) {
+  __shared__ unsigned hist[256];
+  __shared__ unsigned sh_bin, sh_above;
+  __shared__ float red_s[ST / 64];
+  __shared__ int red_i[ST / 64];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const u16* lg = p.logits + (int64_t)row * p.ld;
+
+  unsigned thr = 0;  // candidates: key16 >= thr
+  if (p.top_k > 0 && p.top_k < p.vocab) {
+    unsigned hi = 0, above = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+      if (tid < 256) hist[tid] = 0;
+      __syncthreads();
+      for (int v = tid; v < p.vocab; v += ST) {
+        const u16 b = lg[v];
+        if (is_nan_bf16(b)) continue;
+        const unsigned k = key16(b);
+        if (pass == 0)
+          atomicAdd(&hist[k >> 8], 1u);
+        else if ((k >> 8) == hi)
+          atomicAdd(&hist[k & 255u], 1u);
+      }
+      __syncthreads();
+      if (tid == 0) {  // from the top: the bin in which the count reaches top_k
+        unsigned cum = above;
+        int bin = 255;
+        for (; bin > 0; --bin) {
+          if (cum + hist[bin] >= (unsigned)p.top_k) break;
+          cum += hist[bin];
+        }
+        sh_bin = (unsigned)bin;
+        sh_above = cum;
+      }
+      __syncthreads();
+      if (pass == 0) {
+        hi = sh_bin;
+        above = sh_above;
+      } else {
+        thr = (hi << 8) | sh_bin;
+      }
+      __syncthreads();
+    }
+  }
+
+  const bool greedy = p.inv_temp == 0.f;
+  unsigned pk = 0;
+  if (!greedy) {
+    const unsigned rkey = drop_row_key(drop_site_key(p.seed, (unsigned)DROP_SITE_SAMPLE << 16), p.sample0 + row, 0);
+    pk = rkey ^ ((unsigned)p.pos[row] * 0x9E3779B1u);  // drop_word(rkey, position, v) = fmix32(pk ^ v * 0x85EBCA77)
+  }
+  float best = 0.f;
+  int bi = -1;
+  for (int v = tid; v < p.vocab; v += ST) {
+    const u16 b = lg[v];
+    if (is_nan_bf16(b) || key16(b) < thr) continue;
+    float s = bf2f(b);
+    if (!greedy) {
+      const unsigned word = drop_fmix32(pk ^ ((unsigned)v * 0x85EBCA77u));
+      const float u = __fmul_rn((float)(word >> 9) + 0.5f, 1.1920928955078125e-07f);  // 2^-23, exact
+      const float g = -logf(-logf(u));
+      s = __fadd_rn(__fmul_rn(s, p.inv_temp), g);
+    }
+    if (better(s, v, best, bi)) best = s, bi = v;  // (v ascends: ties keep the earlier index)
+  }
+  // wave, then block: the same rule at every level
+  for (int off = 32; off > 0; off >>= 1) {
+    const float os = __shfl_xor(best, off);
+    const int oi = __shfl_xor(bi, off);
+    if (better(os, oi, best, bi)) best = os, bi = oi;
+  }
+  if ((tid & 63) == 0) red_s[tid >> 6] = best, red_i[tid >> 6] = bi;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < ST / 64; ++w)
+      if (better(red_s[w], red_i[w], best, bi)) best = red_s[w], bi = red_i[w];
+    p.out[row] = bi < 0 ? 0 : bi;  // (a row of NaNs: token 0)
+  }
+}
+
+// one wave per sample, 4 bf16 per lane per step
+__global__ void __launch_bounds__(256) embed_at_kernel(const int64_t* __restrict__ tok, const int* __restrict__ pos,
+                                                       const u16* __restrict__ wte, const u16* __restrict__ wpe,
+                                                       u16* __restrict__ out, int rows, int C, int V, int P) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  int64_t t = tok[row];
+  t = t < 0 ? 0 : (t >= V ? V - 1 : t);
+  int q = pos[row];
+  q = q < 0 ? 0 : (q >= P ? P - 1 : q);  // (the host API keeps positions below block_size)
+  const u16x4* a = reinterpret_cast<const u16x4*>(wte + t * C);
+  const u16x4* b = reinterpret_cast<const u16x4*>(wpe + (int64_t)q * C);
+  u16x4* o = reinterpret_cast<u16x4*>(out + (int64_t)row * C);
+  for (int c = lane; c < C / 4; c += 64) {
+    const u16x4 va = a[c], vb = b[c];
+    u16x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = f2bf(bf2f(va[e]) + bf2f(vb[e]));
+    o[c] = r;
+  }
+}
+
+}  // namespace
+
+void sample_logits_bf16(const void* logits, int rows, int ld, int vocab, float inv_temp, int top_k,
+                        unsigned long long seed, unsigned sample0, const int* pos, int64_t* out, hipStream_t stream) {
+  if (rows <= 0) return;
+  SampleParams p;
+  p.logits = static_cast<const u16*>(logits);
+  p.pos = pos;
+  p.out = out;
+  p.ld = ld, p.vocab = vocab, p.top_k = top_k;
+  p.inv_temp = inv_temp;
+  p.seed = seed;
+  p.sample0 = sample0;
+  hipLaunchKernelGGL(sample_logits_kernel, dim3(rows), dim3(ST), 0, stream, p);
+}
+
+void embedding_at_bf16(const int64_t* tok, const int* pos, const void* wte, const void* wpe, void* out, int rows, int C,
+                       int V, int P, hipStream_t stream) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(embed_at_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, tok, pos,
+                     static_cast<const u16*>(wte), static_cast<const u16*>(wpe), static_cast<u16*>(out), rows, C, V, P);
+}
+
+}  // namespace sdml

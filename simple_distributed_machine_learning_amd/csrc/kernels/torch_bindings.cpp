@@ -3,6 +3,7 @@
 // (a kernel must never see operands its grid does not assume) and launches on the current
 // PyTorch HIP stream, so the ops compose with torch streams, events and hipGraph capture.
 #include <ATen/hip/HIPContext.h>
+#include <climits>
 #include <cmath>
 #include <torch/extension.h>
 
@@ -2087,8 +2088,140 @@ void stream_wait_value32(int64_t ptr, int64_t value) {
   TORCH_CHECK(e == hipSuccess, "hipStreamWaitValue32: ", hipGetErrorString(e));
 }
 
+// ---- generation (attention_decode.hip, linear_decode.hip, sample.hip) ----------------------------------------------
+// qkv [B, 3C] (the new token's fused projection), k_cache / v_cache [B, Smax, H, 64] views (any strides that are
+// multiples of 8 with contiguous channels, the same for both), lens int32 [B]: keys already cached. n_keys: the
+// host's bound lens[b] + 1 <= n_keys (it advances the lengths itself, so it knows them without reading the device).
+// Writes the new k, v at cache row lens[b]; returns the attention output [B, C].
+torch::Tensor attention_decode(torch::Tensor qkv, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor lens,
+                               double scale, int64_t n_keys) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1,
+              "attention_decode: qkv must be a [B, 3C] bf16 device tensor with unit column stride");
+  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.scalar_type() == torch::kBFloat16 &&
+                  v_cache.scalar_type() == torch::kBFloat16 && k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() &&
+                  k_cache.strides() == v_cache.strides(),
+              "attention_decode: k_cache / v_cache must be bf16 device tensors [B, Smax, H, 64] of one layout");
+  const int64_t B = qkv.size(0), Smax = k_cache.size(1), H = k_cache.size(2), C = H * 64;
+  TORCH_CHECK(k_cache.size(3) == 64 && k_cache.stride(3) == 1, "attention_decode: head width 64, contiguous channels");
+  TORCH_CHECK(k_cache.size(0) == B && qkv.size(1) == 3 * C, "attention_decode: qkv ", qkv.sizes(), " does not match a ",
+              k_cache.sizes(), " cache");
+  TORCH_CHECK(k_cache.device() == qkv.device() && v_cache.device() == qkv.device() && lens.device() == qkv.device(),
+              "attention_decode: all tensors on one device");
+  for (int d = 0; d < 3; ++d)
+    TORCH_CHECK(k_cache.stride(d) % 8 == 0 && k_cache.stride(d) >= 0, "attention_decode: cache strides must be multiples of 8");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache),
+              "attention_decode: 16-byte aligned rows required");
+  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() && lens.numel() == B,
+              "attention_decode: lens must be int32 [B] on the device");
+  TORCH_CHECK(n_keys >= 1 && n_keys <= Smax, "attention_decode: the cache is full: ", n_keys, " keys with the new one, ",
+              Smax, " rows (lens[b] + 1 <= n_keys <= Smax)");
+  TORCH_CHECK(B >= 1 && B <= 65535 && H <= 65535, "attention_decode: batch / heads out of the grid's range");
+  sdml::AttnDecodeArgs a;
+  a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
+  auto out = torch::empty({B, C}, qkv.options());
+  auto ws = torch::empty({B * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
+  a.qkv = qkv.data_ptr(), a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr(), a.out = out.data_ptr();
+  a.lens = lens.data_ptr<int>();
+  a.ws_o = ws.data_ptr<float>();
+  a.ws_ml = a.ws_o + B * H * a.max_chunks * 64;
+  a.B = (int)B, a.H = (int)H, a.Smax = (int)Smax;
+  a.ldq = qkv.stride(0), a.sb = k_cache.stride(0), a.ss = k_cache.stride(1), a.sh = k_cache.stride(2);
+  a.scale = (float)scale;
+  sdml::attention_decode_bf16(a, cur_stream());
+  return out;
+}
+
+bool linear_decode_supported_op(int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw) {
+  if (M > INT_MAX || N > INT_MAX || K > INT_MAX || ldx > INT_MAX || ldw > INT_MAX) return false;
+  return sdml::linear_decode_supported((int)M, (int)N, (int)K, (int)ldx, (int)ldw);
+}
+
+// y = x @ w.T (+ bias) (then tanh-GELU); x [M, K], w [N, K] bf16; epi: 0 none, 1 bias, 5 bias + GELU
+torch::Tensor linear_decode(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, int64_t epi) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16 &&
+                  x.dim() == 2 && w.dim() == 2 && x.stride(1) == 1 && w.stride(1) == 1 && x.device() == w.device(),
+              "linear_decode: x [M, K] and w [N, K] must be bf16 tensors on one ROCm device with unit column stride");
+  TORCH_CHECK(x.size(1) == w.size(1), "linear_decode: inner dimensions ", x.sizes(), " vs ", w.sizes());
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  const int64_t ldx = M > 1 ? x.stride(0) : K, ldw = w.stride(0);
+  TORCH_CHECK(linear_decode_supported_op(M, N, K, ldx, ldw) && aligned16(x) && aligned16(w),
+              "linear_decode: unsupported shape M=", M, " N=", N, " K=", K, " (1 <= M <= ", sdml::kLinearDecodeMaxM,
+              ", K % 64 == 0, N % 16 == 0, 16-byte aligned rows; linear_decode_supported)");
+  TORCH_CHECK(epi == sdml::EPI_STORE || epi == sdml::EPI_BIAS || epi == sdml::EPI_BIAS_GELU,
+              "linear_decode: unknown epilogue ", epi);
+  const void* bp = nullptr;
+  if (epi != sdml::EPI_STORE) {
+    TORCH_CHECK(bias.has_value() && bias->defined() && bias->is_cuda() && bias->scalar_type() == torch::kBFloat16 &&
+                    bias->is_contiguous() && bias->numel() == N && bias->device() == x.device(),
+                "linear_decode: bias must be a contiguous bf16 [N] device tensor");
+    bp = bias->data_ptr();
+  }
+  auto y = torch::empty({M, N}, x.options());
+  const size_t wsn = sdml::linear_decode_workspace_floats((int)M, (int)N, (int)K);
+  torch::Tensor ws;
+  if (wsn) ws = torch::empty({(int64_t)wsn}, x.options().dtype(torch::kFloat32));
+  sdml::linear_decode_bf16(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), wsn ? ws.data_ptr<float>() : nullptr, (int)M,
+                           (int)N, (int)K, (int)ldx, (int)ldw, (int)epi, cur_stream());
+  return y;
+}
+
+// tokens [B] int64 from bf16 logits [B, ld] (columns < vocab); temperature 0: greedy. pos: int32 [B] on the device.
+torch::Tensor sample_logits(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, int64_t seed,
+                            int64_t sample0, torch::Tensor pos) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kBFloat16 && logits.dim() == 2 &&
+                  logits.stride(1) == 1 && (logits.size(0) <= 1 || logits.stride(0) >= logits.size(1)),
+              "sample_logits: logits must be a [B, ld] bf16 device tensor with unit column stride");
+  const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : logits.size(1);
+  TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && ld <= INT_MAX, "sample_logits: vocab ", vocab, " outside the ",
+              logits.size(1), " columns");
+  TORCH_CHECK(temperature >= 0.0 && std::isfinite(temperature), "sample_logits: temperature must be >= 0");
+  TORCH_CHECK(seed >= 0 && sample0 >= 0 && sample0 + B <= (int64_t)UINT32_MAX, "sample_logits: seed / sample0 range");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 && pos.is_contiguous() && pos.numel() == B &&
+                  pos.device() == logits.device(),
+              "sample_logits: pos must be int32 [B] on the logits' device");
+  auto out = torch::empty({B}, logits.options().dtype(torch::kInt64));
+  const float inv_temp = temperature > 0.0 ? (float)(1.0 / temperature) : 0.f;
+  TORCH_CHECK(temperature == 0.0 || (inv_temp > 0.f && std::isfinite(inv_temp)), "sample_logits: temperature out of range");
+  const int k = (int)std::max<int64_t>(0, std::min<int64_t>(top_k, vocab));
+  sdml::sample_logits_bf16(logits.data_ptr(), (int)B, (int)ld, (int)vocab, inv_temp, k, (unsigned long long)seed,
+                           (unsigned)sample0, pos.data_ptr<int>(), out.data_ptr<int64_t>(), cur_stream());
+  return out;
+}
+
+// wte[tok[b]] + wpe[pos[b]] -> [B, C] bf16; tok int64 [B], pos int32 [B], both on the device
+torch::Tensor embedding_at(torch::Tensor tok, torch::Tensor pos, torch::Tensor wte, torch::Tensor wpe) {
+  TORCH_CHECK(tok.is_cuda() && tok.scalar_type() == torch::kInt64 && tok.is_contiguous() && tok.dim() == 1,
+              "embedding_at: tok must be a contiguous int64 [B] device tensor");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 && pos.is_contiguous() && pos.numel() == tok.numel(),
+              "embedding_at: pos must be a contiguous int32 [B] device tensor");
+  for (const auto* t : {&wte, &wpe})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 && t->is_contiguous() && t->dim() == 2 &&
+                    t->device() == tok.device(),
+                "embedding_at: wte / wpe must be contiguous bf16 matrices on the tokens' device");
+  const int64_t B = tok.numel(), C = wte.size(1);
+  TORCH_CHECK(wpe.size(1) == C && C % 4 == 0 && pos.device() == tok.device() && wte.size(0) <= INT_MAX,
+              "embedding_at: wte / wpe widths must agree and be a multiple of 4");
+  auto out = torch::empty({B, C}, wte.options());
+  sdml::embedding_at_bf16(tok.data_ptr<int64_t>(), pos.data_ptr<int>(), wte.data_ptr(), wpe.data_ptr(), out.data_ptr(),
+                          (int)B, (int)C, (int)wte.size(0), (int)wpe.size(0), cur_stream());
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "sdml gfx950 HIP kernels";
+  m.def("attention_decode", &attention_decode,
+        "one new token per sample against a KV cache (bf16, d=64): writes k, v at row lens[b], returns [B, C]",
+        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("n_keys"));
+  m.def("attention_decode_chunk", []() { return sdml::kAttnDecodeChunk; }, "keys per wave of attention_decode");
+  m.def("linear_decode", &linear_decode, "x @ w.T (+ bias) (GELU) for M <= 64 rows, weight-streaming (bf16)",
+        py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("epi") = 0);
+  m.def("linear_decode_supported", &linear_decode_supported_op, "shapes linear_decode takes (M, N, K, ldx, ldw)");
+  m.def("linear_decode_splits", [](int64_t N, int64_t K) { return sdml::linear_decode_splits((int)N, (int)K); },
+        "grid-level K splits of linear_decode for (N, K)");
+  m.def("sample_logits", &sample_logits, "greedy / top-k Gumbel-max sampling of bf16 logits rows on the device",
+        py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("seed"),
+        py::arg("sample0"), py::arg("pos"));
+  m.def("embedding_at", &embedding_at, "wte[tok[b]] + wpe[pos[b]] (bf16)");
   m.def("linear_fwd_u8", &linear_fwd_u8, "act(scale * x_u8 @ w.T + b): uint8-pixel first layer", py::arg("x"),
         py::arg("w"), py::arg("b"), py::arg("relu"), py::arg("scale"), py::arg("planes") = py::none(),
         py::arg("planes_valid") = false, py::arg("mask_out") = py::none(), py::arg("wmax_out") = py::none());

@@ -1,0 +1,145 @@
+"""Generation driver: sample token ids from a trained GPT-2 checkpoint.
+
+``python -m simple_distributed_machine_learning_amd.generate --rank 0 --world_size 1 --model gpt2_tiny \
+  --ckpt_dir ckpt --prompt_tokens 1,2,3 --max_new_tokens 16`` (every rank of a pipeline runs the same command, as with
+``train``). The master prints one line of token ids per sample: the prompt followed by the new tokens, separated by
+commas. There is no tokenizer in this project, so token ids are the interface.
+
+Prompts: ``--prompt_tokens 1,2,3`` (repeatable; all of one length), or ``--prompt_from_data N`` with ``--prompt_len L``
+(the first L tokens of the first N test sequences of the synthetic token data, ``--data_seed`` + 1 as in ``train``).
+``--temperature 0`` (default) is greedy; ``--temperature T --top_k K`` samples with noise keyed by (``--seed``, sample,
+position), see parallel/generate.py. ``--metrics`` gets one ``generate`` event: tokens, seconds, tokens/s.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+from typing import List, Optional
+
+import torch
+
+from . import cli
+from .data import SyntheticTokens
+from .models import DEFAULT_STAGES, get_model_spec
+from .parallel import PipelineEngine, init_mesh, shutdown
+from .parallel.generate import generate
+from .train import _device
+from .utils.checkpoint import load_checkpoint
+from .utils.metrics import JsonlMetrics
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="GPT-2 generation",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    cli.add_reference_args(p)
+    g = p.add_argument_group("engine")
+    g.add_argument("--model", default="gpt2", choices=["gpt2", "gpt2_tiny"])
+    g.add_argument("--stages", type=int, default=None, help="pipeline stages (default per model)")
+    g.add_argument("--pp", type=int, default=None, help="ranks per pipeline (default: min(stages, world_size))")
+    g.add_argument("--tp", type=int, default=1, help="refused above 1: generation runs no tensor-parallel stages")
+    g.add_argument("--schedule", default="1f1b", choices=["gpipe", "1f1b", "chimera", "rotate"],
+                   help="the placement the checkpoint was trained with (rotate is refused)")
+    g.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
+    g.add_argument("--backend", default="auto", choices=["auto", "nccl", "rccl", "gloo"])
+    g.add_argument("--timeout", type=float, default=600.0, help="process-group timeout (s)")
+    g.add_argument("--dtype", default="auto", choices=["auto", "fp32", "bf16"])
+    g.add_argument("--seq_len", type=int, default=None, help="sequence length of --prompt_from_data's sequences")
+    g.add_argument("--seed", type=int, default=1, help="run seed: keys the sampler's noise")
+    g.add_argument("--data_seed", type=int, default=1234)
+    g.add_argument("--ckpt_dir", default=None, help="checkpoint to load (train --ckpt_dir); none: initial weights")
+    g.add_argument("--metrics", default=None, help="JSONL metrics file (rank 0)")
+    s = p.add_argument_group("generation")
+    s.add_argument("--prompt_tokens", action="append", default=None, metavar="1,2,3",
+                   help="one prompt as comma-separated token ids (repeatable; equal lengths)")
+    s.add_argument("--prompt_from_data", type=int, default=0, metavar="N",
+                   help="take the prompts from the first N test sequences of the synthetic token data")
+    s.add_argument("--prompt_len", type=int, default=1, help="tokens per --prompt_from_data prompt")
+    s.add_argument("--max_new_tokens", type=int, default=16)
+    s.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
+    s.add_argument("--top_k", type=int, default=0, help="sample among the k most likely tokens (0: all)")
+    return p
+
+
+def parse_args(argv: Optional[List[str]] = None):
+    import os
+
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.rank is None and "RANK" in os.environ:
+        args.rank = int(os.environ["RANK"])
+    if args.world_size is None:
+        args.world_size = int(os.environ.get("WORLD_SIZE", "2"))  # (the reference's default, as in train)
+    if args.rank is None:
+        parser.error("--rank is required (or RANK in the environment)")
+    if args.backend == "rccl":
+        args.backend = "nccl"
+    if bool(args.prompt_tokens) == bool(args.prompt_from_data):
+        parser.error("give either --prompt_tokens (repeatable) or --prompt_from_data N")
+    return args
+
+
+def _prompts(args, spec) -> torch.Tensor:
+    if args.prompt_tokens:
+        try:
+            rows = [[int(t) for t in p.split(",") if t.strip() != ""] for p in args.prompt_tokens]
+        except ValueError:
+            raise SystemExit("--prompt_tokens takes comma-separated integers")
+        if len({len(r) for r in rows}) != 1 or not rows[0]:
+            raise SystemExit("--prompt_tokens: all prompts of one call must have the same, non-zero length")
+        t = torch.tensor(rows, dtype=torch.int64)
+        if int(t.min()) < 0 or int(t.max()) >= spec.vocab_size:
+            raise SystemExit(f"--prompt_tokens: token ids must be in [0, {spec.vocab_size})")
+        return t
+    S = max(args.prompt_len, spec.seq_len or args.seq_len or 64)
+    ds = SyntheticTokens(args.prompt_from_data, S, spec.vocab_size, seed=args.data_seed + 1)
+    return ds.inputs(0, args.prompt_from_data)[:, :args.prompt_len].contiguous()
+
+
+def run(args) -> dict:
+    cli.export_env(args)
+    device = _device(args)
+    stages = args.stages or DEFAULT_STAGES[args.model]
+    pp = args.pp or min(stages, max(1, args.world_size // max(1, args.tp)))
+    pp = max(1, min(pp, args.world_size // max(1, args.tp)))
+    while stages % pp:
+        pp -= 1
+    backend = None if args.backend == "auto" else args.backend
+    mesh = init_mesh(pp=pp, schedule_kind=args.schedule, backend=backend, timeout_s=args.timeout, rank=args.rank,
+                     world_size=args.world_size, device=device, tp=args.tp)
+    dt = {"fp32": torch.float32, "bf16": torch.bfloat16}.get(args.dtype)
+    kw = {"dtype": dt} if dt is not None and args.model == "gpt2_tiny" else {}
+    spec = get_model_spec(args.model, stages, seq_len=args.seq_len, **kw)
+    if dt is not None and spec.param_dtype != dt:
+        raise SystemExit(f"--dtype {args.dtype} is not supported for --model {args.model}")
+    engine = PipelineEngine(spec, mesh, schedule_kind=args.schedule, num_microbatches=1, seed=args.seed)
+    if args.ckpt_dir:
+        load_checkpoint(engine, args.ckpt_dir)
+    prompts = _prompts(args, spec)
+    metrics = JsonlMetrics(args.metrics if mesh.is_master() else None, mesh.rank)
+    try:
+        t0 = time.perf_counter()
+        out = generate(engine, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
+                       seed=args.seed)
+        rows = out.cpu().tolist()  # (the read-back ends the timed region)
+        dt_s = time.perf_counter() - t0
+    except ValueError as e:  # the refusals (tp, dp, rotate, lengths): their message, not a traceback
+        shutdown(mesh)
+        raise SystemExit(str(e))
+    n_new = len(rows) * args.max_new_tokens
+    if mesh.is_master():
+        for r in rows:
+            print(",".join(str(t) for t in r), flush=True)
+        metrics.log(event="generate", samples=len(rows), prompt_len=prompts.shape[1], tokens=n_new, seconds=dt_s,
+                    tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k)
+    return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    res = run(parse_args(argv))
+    shutdown(res["mesh"])
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -29,7 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .base import ModelSpec, PipelineStage
-from ..ops.linear import Linear, linear, lm_head, mlp_gelu
+from ..ops.decode import attention_decode, embedding_at, linear_decode
+from ..ops.linear import Linear, _w_padded, linear, lm_head, mlp_gelu
 from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
                              dropout_threshold)
 from ..ops.transformer import (Drop, LayerNorm, add_layer_norm, causal_attention, cross_entropy_sum, dropout_add,
@@ -265,6 +266,113 @@ class GPT2Stage(PipelineStage):
             else:
                 x, y = add_layer_norm(x, m, nxt, dm)
         return lm_head(y, self.lm_head.weight) if last else x
+
+    # ---- generation: KV cache, prefill, one decode step (ops/decode.py; parallel/generate.py drives them) ----------
+    def new_cache(self, B: int, Smax: int) -> "KVCache":
+        """An empty cache for B samples and up to Smax positions: K and V [B, Smax, H, D] per local layer, one
+        device-side length."""
+        if Smax > self.cfg.block_size:
+            raise ValueError(f"a cache of {Smax} positions exceeds block_size={self.cfg.block_size}")
+        if getattr(self, "tp", None) is not None:
+            raise ValueError("generation does not run tensor-parallel stages (tp > 1)")
+        p = next(self.parameters())
+        H, D = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        mk = lambda: torch.empty((B, Smax, H, D), dtype=p.dtype, device=p.device)  # noqa: E731
+        n = len(self.h)
+        return KVCache([mk() for _ in range(n)], [mk() for _ in range(n)],
+                       torch.zeros(B, dtype=torch.int32, device=p.device), 0, Smax)
+
+    def _head_logits(self, y):
+        """[B, ld] logits of rows y [B, C]: ld is the padded vocabulary where the weight sits in row-padded storage
+        (pad columns exact zeros), else the vocabulary."""
+        w = self.lm_head.weight
+        wp = _w_padded(w) if (w.is_cuda and w.dtype == torch.bfloat16) else None
+        return linear_decode(y, w if wp is None else wp)
+
+    @torch.no_grad()
+    def prefill(self, x, cache: "KVCache"):
+        """The prompt through this stage: today's forward (flash attention at the prompt length, no dropout) plus the
+        copies of every layer's k / v into the cache. x: tokens [B, S0] on stage 0, else [B, S0, C]. Returns the
+        boundary [B, S0, C], or on the last stage the logits [B, ld] of the last position only."""
+        if self.stage_id == 0:
+            x = embedding(x, self.wte.weight, self.wpe.weight)
+        B, S, C = x.shape
+        if cache.n != 0 or S > cache.smax or B != cache.lens.shape[0]:
+            raise ValueError(f"prefill of {B} x {S} tokens into a cache of {cache.lens.shape[0]} x {cache.smax} "
+                             f"holding {cache.n}")
+        last = self.stage_id == self.num_stages - 1
+        blocks = list(self.h.values())
+        H = self.cfg.n_head
+        y = None
+        if blocks:
+            x, y = layer_norm_pass(x, blocks[0].ln_1)
+        for i, blk in enumerate(blocks):
+            qkv = blk.attn.c_attn(y)
+            cache.k[i][:, :S].copy_(qkv[..., C:2 * C].view(B, S, H, C // H))
+            cache.v[i][:, :S].copy_(qkv[..., 2 * C:].view(B, S, H, C // H))
+            a = blk.attn.c_proj(causal_attention(qkv, H))
+            x, y = add_layer_norm(x, a, blk.ln_2)
+            m = blk.mlp(y)
+            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
+            if nxt is None:
+                x = x + m
+            else:
+                x, y = add_layer_norm(x, m, nxt)
+        cache.lens.fill_(S)
+        cache.n = S
+        if not last:
+            return x
+        if y is None:
+            y = self.ln_f(x)
+        return self._head_logits(y[:, -1].contiguous())
+
+    @torch.no_grad()
+    def decode_step(self, x, cache: "KVCache"):
+        """One new token per sample. x: tokens [B] on stage 0, else [B, C]. Appends the token's k / v to the cache,
+        advances the device-side length, returns [B, C] or on the last stage the logits [B, ld]. No host
+        synchronisation: positions come from ``cache.lens``."""
+        if cache.n + 1 > cache.smax:
+            raise ValueError(f"the cache is full ({cache.n} of {cache.smax} positions)")
+        if self.stage_id == 0:
+            x = embedding_at(x, cache.lens, self.wte.weight, self.wpe.weight)
+        last = self.stage_id == self.num_stages - 1
+        blocks = list(self.h.values())
+        H = self.cfg.n_head
+        y = None
+        if blocks:
+            x, y = layer_norm_pass(x, blocks[0].ln_1)
+        for i, blk in enumerate(blocks):
+            at, mlp = blk.attn, blk.mlp
+            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias)
+            a = attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, cache.n + 1)
+            a = linear_decode(a, at.c_proj.weight, at.c_proj.bias)
+            x, y = add_layer_norm(x, a, blk.ln_2)
+            m = linear_decode(linear_decode(y, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True), mlp.c_proj.weight,
+                              mlp.c_proj.bias)
+            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
+            if nxt is None:
+                x = x + m
+            else:
+                x, y = add_layer_norm(x, m, nxt)
+        cache.lens.add_(1)
+        cache.n += 1
+        if not last:
+            return x
+        if y is None:
+            y = self.ln_f(x)
+        return self._head_logits(y)
+
+
+@dataclass
+class KVCache:
+    """A stage's generation state: per local layer K and V [B, Smax, H, D]; ``lens`` int32 [B] on the device (keys
+    cached per sample, what the kernels read); ``n`` the same count on the host (all samples advance together), so
+    the bounds are checked without reading the device."""
+    k: list
+    v: list
+    lens: torch.Tensor
+    n: int
+    smax: int
 
 
 def gpt2_spec(num_stages: int = 2, cfg: GPT2Config = None, seq_len: int = None, dtype=torch.bfloat16,

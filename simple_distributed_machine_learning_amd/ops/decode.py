@@ -1,0 +1,93 @@
+"""Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, linear_decode.hip,
+sample.hip) and their torch twins.
+
+Dispatch: ROCm bf16 tensors (head width 64 for the attention) run the hand-written kernels, and a shape the kernels do
+not take is an error there, never a library call. CPU tensors, fp32 and other head widths run the twins below, which
+define the semantics. Nothing here builds an autograd graph: generation runs under ``torch.no_grad()``.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn.functional as F
+
+from .._native import kernels
+from . import reference as _ref
+
+EPI_STORE, EPI_BIAS, EPI_BIAS_GELU = 0, 1, 5  # csrc/kernels/kernels.h GemmEpi
+LINEAR_DECODE_MAX_M = 64  # kLinearDecodeMaxM
+
+
+def _hip_bf16(*ts) -> bool:
+    return all(t.is_cuda and t.dtype == torch.bfloat16 for t in ts)
+
+
+def linear_decode_supported(M: int, N: int, K: int, ldx: int = None, ldw: int = None) -> bool:
+    """Shapes the weight-streaming kernel takes: 1 <= M <= 64, K % 64 == 0, N % 16 == 0, row strides % 8 == 0."""
+    return bool(kernels().linear_decode_supported(M, N, K, K if ldx is None else ldx, K if ldw is None else ldw))
+
+
+def linear_decode(x, w, b=None, gelu: bool = False):
+    """y [M, N] = x [M, K] w[N, K]^T (+ b) (then tanh-GELU; needs b). ROCm bf16: linear_decode.hip for M <= 64 (W
+    streamed once over the whole chip), gemm_bf16.hip above that; anything else: torch."""
+    if gelu and b is None:
+        raise ValueError("linear_decode: the GELU epilogue comes with a bias")
+    if _hip_bf16(x, w):
+        epi = EPI_BIAS_GELU if gelu else (EPI_BIAS if b is not None else EPI_STORE)
+        if x.shape[0] <= LINEAR_DECODE_MAX_M:
+            return kernels().linear_decode(x, w, b, epi)
+        return kernels().gemm_bf16(x, w, b, False, epi)[0]
+    y = F.linear(x, w, b)
+    return F.gelu(y, approximate="tanh") if gelu else y
+
+
+def attention_decode_ref(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int):
+    """The twin: write the new k, v at cache row lens[b]; softmax(q K[0..lens[b]]^T / sqrt(D)) V[0..lens[b]] in fp32.
+    Rows past lens[b] are selected away (a cache from torch.empty may hold NaN patterns)."""
+    B, C3 = qkv.shape
+    C = C3 // 3
+    D = C // n_head
+    q, k, v = (qkv[:, i * C:(i + 1) * C].view(B, n_head, D) for i in range(3))
+    idx = lens.to(torch.int64)
+    rows = torch.arange(B, device=qkv.device)
+    k_cache[rows, idx] = k
+    v_cache[rows, idx] = v
+    live = torch.arange(n_keys, device=qkv.device)[None, :] <= idx[:, None]  # [B, n_keys]
+    kc = torch.where(live[:, :, None, None], k_cache[:, :n_keys], torch.zeros_like(k_cache[:, :n_keys])).float()
+    vc = torch.where(live[:, :, None, None], v_cache[:, :n_keys], torch.zeros_like(v_cache[:, :n_keys])).float()
+    s = torch.einsum("bhd,bshd->bhs", q.float(), kc) * (1.0 / math.sqrt(D))
+    p = torch.softmax(s.masked_fill(~live[:, None, :], -math.inf), dim=-1)
+    return torch.einsum("bhs,bshd->bhd", p, vc).to(qkv.dtype).reshape(B, C)
+
+
+def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int):
+    """One new token per sample against a KV cache. qkv [B, 3C]: the token's fused projection; k_cache / v_cache
+    [B, Smax, H, D] (views with any row strides); lens int32 [B] on the device: keys already cached. Writes the new
+    k, v to cache row lens[b] and returns the attention output [B, C] over keys 0..lens[b]. ``lens`` is not changed:
+    the caller advances it once per step, on the device. ``n_keys`` is the host's bound lens[b] + 1 <= n_keys (the
+    caller counts the steps itself, so no length is read back); n_keys <= Smax or a ValueError."""
+    Smax = k_cache.shape[1]
+    if not 1 <= n_keys <= Smax:
+        raise ValueError(f"attention_decode: {n_keys} keys with the new one, but the cache has {Smax} rows")
+    D = k_cache.shape[-1]
+    if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
+        return kernels().attention_decode(qkv, k_cache, v_cache, lens, 1.0 / math.sqrt(D), int(n_keys))
+    return attention_decode_ref(qkv, k_cache, v_cache, lens, n_head, n_keys)
+
+
+def embedding_at(tok, pos, wte, wpe):
+    """wte[tok[b]] + wpe[pos[b]] -> [B, C] for tok int64 [B] and pos int32 [B] on the device."""
+    if _hip_bf16(wte, wpe) and tok.is_cuda and wte.shape[1] % 4 == 0:
+        return kernels().embedding_at(tok.contiguous(), pos, wte, wpe)
+    return F.embedding(tok, wte) + F.embedding(pos.to(torch.int64), wpe)
+
+
+def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int, sample0: int, positions):
+    """Tokens int64 [B] from logits [B, ld]: greedy at temperature 0, else top-k Gumbel-max keyed by
+    (seed, sample0 + row, positions[row], token) (ops/reference.py sample_logits is the definition). ROCm bf16: the
+    on-device sampler, no host synchronisation."""
+    if _hip_bf16(logits):
+        return kernels().sample_logits(logits, int(vocab), float(temperature), int(top_k), int(seed), int(sample0),
+                                       positions)
+    return _ref.sample_logits(logits, vocab, temperature, top_k, seed, sample0, positions)

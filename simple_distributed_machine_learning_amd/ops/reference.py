@@ -289,3 +289,67 @@ def gpt2_site_keep(seed: int, ctr, site: int, layer: int, sample0: int, B: int, 
     dev = device if device is not None else (ctr.device if ctr is not None else "cpu")
     smp = torch.arange(sample0, sample0 + B, dtype=torch.int64, device=dev)
     return gpt2_dropout_keep(gpt2_dropout_row_keys(seed, ctr, site, layer, smp, torch.zeros_like(smp)), S, C, T)
+
+
+# ---- generation: the sampler (csrc/kernels/sample.hip) ----------------------------------------
+# The same counter hash, site DROP_SITE_SAMPLE, layer 0, head 0, a = the position of the token being drawn, the
+# vocabulary id in the b4 slot (one word per candidate), no step counter: a drawn token is a function of
+# (seed, sample, position, logits) and of nothing else.
+DROP_SITE_SAMPLE = 5
+
+
+def sample_uniforms(seed: int, samples, positions, vocab: int):
+    """u [B, vocab] float32 for samples [B] and positions [B] (int tensors on one device):
+    u = ((word >> 9) + 0.5) * 2^-23, word = fmix32(rkey ^ position * 0x9E3779B1 ^ v * 0x85EBCA77). Every u is exact in
+    fp32 and lies in [2^-24, 1 - 2^-24]."""
+    samples = samples.to(torch.int64)
+    rkey = gpt2_dropout_row_keys(seed, None, DROP_SITE_SAMPLE, 0, samples, torch.zeros_like(samples))
+    a = (positions.to(torch.int64).to(samples.device) * 0x9E3779B1) & _M32
+    v = (torch.arange(vocab, dtype=torch.int64, device=samples.device) * 0x85EBCA77) & _M32
+    word = _fmix32(rkey[:, None] ^ a[:, None] ^ v[None, :])
+    return ((word >> 9).to(torch.float32) + 0.5) * (2.0 ** -23)
+
+
+def gumbel_from_uniform(u):
+    """g = -log(-log u) in the dtype of u."""
+    return -torch.log(-torch.log(u))
+
+
+def top_k_candidates(logits, top_k: int):
+    """[B, V] bool: the tokens whose logit is >= the k-th largest logit value of their row (ties at the boundary are
+    all candidates); top_k <= 0 or >= V: every token. NaN logits are never candidates."""
+    z = torch.nan_to_num(logits.float(), nan=-math.inf)
+    V = z.shape[1]
+    ok = ~torch.isnan(logits)
+    if top_k <= 0 or top_k >= V:
+        return ok
+    kth = torch.topk(z, int(top_k), dim=1).values[:, -1:]
+    return ok & (z >= kth)
+
+
+def _first_argmax(score, cand):
+    """Index of the largest score among the candidates, the lowest index on ties (token 0 for a row without any)."""
+    s = torch.where(cand, score, torch.full_like(score, -math.inf))
+    V = s.shape[1]
+    idx = torch.arange(V, device=s.device)[None, :].expand_as(s)
+    hit = cand & (s == s.amax(1, keepdim=True))
+    tok = torch.where(hit, idx, torch.full_like(idx, V)).amin(1)
+    return torch.where(tok == V, torch.zeros_like(tok), tok)
+
+
+def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int, sample0: int, positions):
+    """Tokens [B] int64 from logits [B, ld] (columns < vocab take part). temperature == 0: greedy (argmax, lowest index
+    on ties). temperature > 0: Gumbel-max over the top-k candidates, argmax_v(l_v * (1 / T) + g_v) in fp32 with one
+    multiply and one add, noise from sample_uniforms for samples sample0 + row and the given positions [B]."""
+    if temperature < 0:
+        raise ValueError(f"temperature must be >= 0, got {temperature}")
+    z = logits[:, :vocab]
+    cand = top_k_candidates(z, top_k)
+    zf = torch.nan_to_num(z.float(), nan=-math.inf)
+    if temperature == 0:
+        return _first_argmax(zf, cand)
+    B = z.shape[0]
+    samples = torch.arange(sample0, sample0 + B, dtype=torch.int64, device=z.device)
+    g = gumbel_from_uniform(sample_uniforms(seed, samples, positions, vocab))
+    inv_t = torch.tensor(1.0 / float(temperature), dtype=torch.float32, device=z.device)
+    return _first_argmax(zf * inv_t + g, cand)

@@ -1,0 +1,224 @@
+"""GPT-2 small generation on one MI355X: the decode kernels next to the library calls for the same work, and the
+whole decode loop, hand-written against library-substituted, alternated in one process over --rounds rounds.
+
+    python tools/bench_generate.py [--B 16] [--ctx 512] [--rounds 3] [--sweep]
+        [--out_kernels profiles/generate_kernels.jsonl] [--out_loop profiles/generate_gpt2.jsonl]
+
+Per kernel (one JSON line per kernel, shape and round): the time of one call, taken as a device-event window around
+--reps back-to-back calls, and the achieved GB/s of the bytes that must move: W for the projections (x and y are
+below 1 % of it), K + V for the attention. Every call of a window reads another copy of its operand, the copies
+totalling more than the 256 MB last-level cache, as a decode step streams each layer's weights and cache once. A
+window is the larger of the device time and the host's enqueue time of its calls: at these sizes (microseconds) the
+small shapes sit on the enqueue floor, and the kernels' own durations come from a `rocprofv3 --kernel-trace --stats`
+run of this tool (README "Generation").
+  * linear_decode / torch.addmm / gemm_bf16 at M = B rows, the four GPT-2 shapes and the lm_head
+  * attention_decode / F.scaled_dot_product_attention with a one-row query over the cached keys
+Decode loop: --steps steps of the 12-layer model (2 stages in one process) from a cache already holding ctx keys,
+greedy sampling on the device, tokens/s = B * steps / seconds (host clock around a device synchronise). "lib" is the
+same loop with torch.addmm, index_put + scaled_dot_product_attention, F.embedding and argmax in place of the four
+hand kernels (the LayerNorm kernels are the same in both). The gate: hand >= lib at --B 16 --ctx 512.
+--sweep adds B in {1, 16, 64} x ctx in {128, 1024}.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from simple_distributed_machine_learning_amd import _native  # noqa: E402
+from simple_distributed_machine_learning_amd.models import get_model_spec  # noqa: E402
+from simple_distributed_machine_learning_amd.ops.decode import sample_logits  # noqa: E402
+from simple_distributed_machine_learning_amd.ops.transformer import add_layer_norm, layer_norm_pass  # noqa: E402
+from simple_distributed_machine_learning_amd.parallel import PipelineEngine, init_mesh  # noqa: E402
+
+DEV = torch.device("cuda", 0)
+BF = torch.bfloat16
+LLC_BYTES = 320 << 20  # operand copies per window: beyond the 256 MB last-level cache
+SHAPES = {"c_attn": (2304, 768), "attn_proj": (768, 768), "c_fc": (3072, 768), "mlp_proj": (768, 3072),
+          "lm_head": (50304, 768)}
+
+
+def window(fn, reps):
+    """ms per call of fn(i), i = 0 .. reps - 1, from one device-event window."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(reps):
+        fn(i)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def bench_kernels(B, ctxs, rounds, reps, emit):
+    K = _native.kernels()
+    for name, (N, Kd) in SHAPES.items():
+        copies = max(2, min(reps, LLC_BYTES // (N * Kd * 2) + 1))
+        w = torch.randn(copies, N, Kd, device=DEV, dtype=BF) * 0.02
+        b = torch.randn(N, device=DEV, dtype=BF)
+        x = torch.randn(B, Kd, device=DEV, dtype=BF)
+        fns = {"linear_decode": lambda i: K.linear_decode(x, w[i % copies], b, 1),
+               "torch.addmm": lambda i: torch.addmm(b, x, w[i % copies].t())}
+        if name in ("c_attn", "c_fc"):
+            fns["gemm_bf16"] = lambda i: K.gemm_bf16(x, w[i % copies], b, False, 1)
+        for fn in fns.values():
+            window(fn, copies)  # warm-up: every copy touched, code objects loaded, the library's algorithm picked
+        for r in range(rounds):
+            for kname, fn in fns.items():  # alternated
+                ms = window(fn, reps)
+                emit({"kernel": kname, "shape": name, "M": B, "N": N, "K": Kd, "round": r, "us": round(ms * 1e3, 2),
+                      "GB_per_s": round(N * Kd * 2 / (ms * 1e-3) / 1e9, 1), "bytes": N * Kd * 2, "copies": copies})
+        del w
+    H, D = 12, 64
+    for ctx in ctxs:
+        Smax = ctx + 1
+        per = B * Smax * H * D * 2 * 2
+        copies = max(2, min(reps, LLC_BYTES // per + 1))
+        kc = torch.randn(copies, B, Smax, H, D, device=DEV, dtype=BF)
+        vc = torch.randn(copies, B, Smax, H, D, device=DEV, dtype=BF)
+        qkv = torch.randn(B, 3 * H * D, device=DEV, dtype=BF)
+        lens = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+        q4 = qkv[:, :H * D].view(B, H, 1, D)
+
+        def lib(i):
+            k, v = kc[i % copies].transpose(1, 2), vc[i % copies].transpose(1, 2)
+            return F.scaled_dot_product_attention(q4, k, v)
+
+        fns = {"attention_decode": lambda i: K.attention_decode(qkv, kc[i % copies], vc[i % copies], lens, 0.125, Smax),
+               "F.scaled_dot_product_attention": lib}
+        for fn in fns.values():
+            window(fn, copies)
+        nbytes = B * (ctx + 1) * H * D * 2 * 2
+        for r in range(rounds):
+            for kname, fn in fns.items():
+                ms = window(fn, reps)
+                emit({"kernel": kname, "B": B, "H": H, "ctx": ctx, "round": r, "us": round(ms * 1e3, 2),
+                      "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1), "bytes": nbytes, "copies": copies})
+        del kc, vc
+
+
+# ---- the decode loop ---------------------------------------------------------------------------------------------
+def lib_decode_step(stage, x, cache):
+    """models/gpt2.py decode_step with library calls in place of the hand kernels."""
+    cfg = stage.cfg
+    H, C = cfg.n_head, cfg.n_embd
+    B = x.shape[0]
+    rows = torch.arange(B, device=x.device)
+    if stage.stage_id == 0:
+        x = F.embedding(x, stage.wte.weight) + F.embedding(cache.lens.long(), stage.wpe.weight)
+    last = stage.stage_id == stage.num_stages - 1
+    blocks = list(stage.h.values())
+    n = cache.n + 1
+    x, y = layer_norm_pass(x, blocks[0].ln_1)
+    for i, blk in enumerate(blocks):
+        at, mlp = blk.attn, blk.mlp
+        qkv = torch.addmm(at.c_attn.bias, y, at.c_attn.weight.t())
+        q, k, v = (qkv[:, j * C:(j + 1) * C].view(B, H, C // H) for j in range(3))
+        idx = cache.lens.long()
+        cache.k[i][rows, idx] = k
+        cache.v[i][rows, idx] = v
+        a = F.scaled_dot_product_attention(q[:, :, None], cache.k[i][:, :n].transpose(1, 2),
+                                           cache.v[i][:, :n].transpose(1, 2)).reshape(B, C)
+        a = torch.addmm(at.c_proj.bias, a, at.c_proj.weight.t())
+        x, y = add_layer_norm(x, a, blk.ln_2)
+        hdn = F.gelu(torch.addmm(mlp.c_fc.bias, y, mlp.c_fc.weight.t()), approximate="tanh")
+        m = torch.addmm(mlp.c_proj.bias, hdn, mlp.c_proj.weight.t())
+        nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (stage.ln_f if last else None)
+        if nxt is None:
+            x = x + m
+        else:
+            x, y = add_layer_norm(x, m, nxt)
+    cache.lens.add_(1)
+    cache.n += 1
+    return y @ stage.lm_head.weight.t() if last else x
+
+
+@torch.no_grad()
+def run_loop(engine, B, ctx, steps, hand):
+    """Seconds of `steps` decode steps from caches holding ctx keys (random contents; greedy sampling); where ctx +
+    steps would pass block_size the loop starts at block_size - steps keys and ends at block_size."""
+    stages = [engine.stages[s] for s in range(engine.P)]
+    ctx = min(ctx, stages[0].cfg.block_size - steps)
+    caches = [st.new_cache(B, ctx + steps) for st in stages]
+    for c in caches:
+        for t in c.k + c.v:
+            t.normal_()
+        c.lens.fill_(ctx)
+        c.n = ctx
+    V = stages[0].cfg.vocab_size
+    tok = torch.randint(0, V, (B,), device=DEV)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        x = tok
+        for st, c in zip(stages, caches):
+            x = st.decode_step(x, c) if hand else lib_decode_step(st, x, c)
+        tok = sample_logits(x, V, 0.0, 0, 0, 0, caches[-1].lens) if hand else x[:, :V].argmax(-1)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def bench_loop(engine, B, ctx, steps, rounds, emit, gate):
+    for hand in (True, False):
+        run_loop(engine, B, ctx, 8, hand)  # warm-up of both paths at this shape
+    tps = {True: [], False: []}
+    for r in range(rounds):
+        for hand in (True, False):  # alternated
+            s = run_loop(engine, B, ctx, steps, hand)
+            tps[hand].append(B * steps / s)
+            emit({"loop": "hand" if hand else "lib", "B": B, "ctx": ctx, "steps": steps, "round": r,
+                  "ms_per_step": round(s / steps * 1e3, 4), "tokens_per_s": round(B * steps / s, 1)})
+    h, l = statistics.median(tps[True]), statistics.median(tps[False])
+    rec = {"summary": "decode loop", "B": B, "ctx": ctx, "hand_tokens_per_s": round(h, 1),
+           "lib_tokens_per_s": round(l, 1), "hand_over_lib": round(h / l, 3)}
+    if gate:
+        rec["gate_hand_at_least_lib"] = bool(h >= l)
+    emit(rec)
+    return h >= l
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=16)
+    ap.add_argument("--ctx", type=int, default=512)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=200, help="calls per kernel timing window")
+    ap.add_argument("--steps", type=int, default=128, help="decode steps per loop timing")
+    ap.add_argument("--sweep", action="store_true", help="also B in {1, 16, 64} x ctx in {128, 1024}")
+    ap.add_argument("--no_kernels", action="store_true")
+    ap.add_argument("--out_kernels", default="profiles/generate_kernels.jsonl")
+    ap.add_argument("--out_loop", default="profiles/generate_gpt2.jsonl")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_generate.py measures on the GPU; none is visible")
+    for p in (a.out_kernels, a.out_loop):
+        os.makedirs(os.path.dirname(p) or ".", exist_ok=True)
+    ok = True
+    with open(a.out_kernels, "w") as fk, open(a.out_loop, "w") as fl:
+        def emitter(f):
+            def emit(rec):
+                line = json.dumps(rec)
+                print(line, flush=True)
+                f.write(line + "\n")
+                f.flush()
+            return emit
+
+        if not a.no_kernels:
+            bench_kernels(a.B, sorted({128, a.ctx, 1024}), a.rounds, a.reps, emitter(fk))
+        mesh = init_mesh(pp=1, schedule_kind="1f1b", rank=0, world_size=1, device=DEV)
+        engine = PipelineEngine(get_model_spec("gpt2", 2), mesh, schedule_kind="1f1b", num_microbatches=1)
+        engine.eval()
+        ok = bench_loop(engine, a.B, a.ctx, a.steps, a.rounds, emitter(fl), gate=True)
+        if a.sweep:
+            for B in (1, 16, 64):
+                for ctx in (128, 1024):
+                    bench_loop(engine, B, ctx, a.steps, a.rounds, emitter(fl), gate=False)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
