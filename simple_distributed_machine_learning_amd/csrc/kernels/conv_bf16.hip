@@ -78,8 +78,9 @@ struct ConvArgs {
 // [BM][BN + 8] (padded rows), then written out as 16-B row chunks: a thread owns one 8-channel chunk of
 // BM / (NT / (BN / 8)) rows, so every global access is a full 16-B vector and the output row's address
 // (rowoff: element offset of channel n0 of tile row r in y, < 0 = no such row) is decoded once per row,
-// not once per element. EPI = 1 adds the optional addend (same layout as y; y = bf16(bf16(acc) + add),
-// the rounding of the separate add it replaces) and the optional BatchNorm partials of the stored y:
+// not once per element. EPI = 1 adds the optional addend (same layout as y) to the fp32 accumulator, one rounding:
+// y = bf16(acc + add) (rounding the accumulator first, bf16(bf16(acc) + add), leaves that rounding's error, which is
+// many ulps of the result where convolution and addend cancel), and the optional BatchNorm partials of the stored y:
 // per channel, sums of y and y^2 over the tile's rows in a fixed order (the thread's rows, then the
 // row groups through LDS), written to part_row[0][0..BN) and part_row[0][Co..Co+BN) - the forward
 // BatchNorm (batchnorm_nhwc.hip) then finalizes these rows instead of re-reading y. With bb.x set the two sums
@@ -99,6 +100,34 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[TM][2], int wm, i
   const int h = lane >> 5;
   const int t = threadIdx.x, c = t % CPR, r0 = t / CPR;
   __syncthreads();
+  // every global operand of the thread's rows is loaded up front (one memory latency for the whole
+  // epilogue instead of one per row: the stores to y would otherwise order each row's loads after the last row's)
+  long long offs[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) offs[k] = rowoff(r0 + k * RPP);
+  const bool bwd = EPI == 1 && part_row && bb.x;
+  const bool has_add = EPI == 1 && add;
+  u16x8 xv[NR], yv[NR];
+  float mu[8], rs[8], sc[8], sh[8];  // backward statistics (bb.x): this thread's 8 channels' coefficients
+  if constexpr (EPI == 1) {
+    // the addend goes through the LDS image (16-B row chunks in, the accumulator layout out), so it is added to the
+    // fp32 accumulator and the sum is rounded once: y = bf16(acc + add)
+    if (has_add) {
+      u16x8 av[NR];
+#pragma unroll
+      for (int k = 0; k < NR; ++k)
+        av[k] = *reinterpret_cast<const u16x8*>(add + (offs[k] < 0 ? 0 : offs[k]) + 8 * c);
+#pragma unroll
+      for (int k = 0; k < NR; ++k) *reinterpret_cast<u16x8*>(lds + (r0 + k * RPP) * LP + 8 * c) = av[k];
+    }
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const long long o = (offs[k] < 0 ? 0 : offs[k]) + 8 * c;
+      xv[k] = bwd ? *reinterpret_cast<const u16x8*>(bb.x + o) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      yv[k] = bwd && bb.relu == 1 ? *reinterpret_cast<const u16x8*>(bb.y + o) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    if (has_add) __syncthreads();
+  }
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -107,25 +136,12 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[TM][2], int wm, i
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = wm * WTM + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-        lds[row * LP + col] = f2bf(acc[i][j][r]);
+        float v = acc[i][j][r];
+        if (has_add) v += bf2f(lds[row * LP + col]);  // (this thread alone reads and rewrites the slot)
+        lds[row * LP + col] = f2bf(v);
       }
     }
-  // every global operand of the thread's rows is loaded before the barrier (one memory latency for the whole
-  // epilogue instead of one per row: the stores to y would otherwise order each row's loads after the last row's)
-  long long offs[NR];
-#pragma unroll
-  for (int k = 0; k < NR; ++k) offs[k] = rowoff(r0 + k * RPP);
-  const bool bwd = EPI == 1 && part_row && bb.x;
-  u16x8 av[NR], xv[NR], yv[NR];
-  float mu[8], rs[8], sc[8], sh[8];  // backward statistics (bb.x): this thread's 8 channels' coefficients
   if constexpr (EPI == 1) {
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const long long o = (offs[k] < 0 ? 0 : offs[k]) + 8 * c;
-      av[k] = add ? *reinterpret_cast<const u16x8*>(add + o) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      xv[k] = bwd ? *reinterpret_cast<const u16x8*>(bb.x + o) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      yv[k] = bwd && bb.relu == 1 ? *reinterpret_cast<const u16x8*>(bb.y + o) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    }
     if (bwd) {
       const u16x8 gm = *reinterpret_cast<const u16x8*>(bb.gamma + n0 + 8 * c);
       const u16x8 bt = *reinterpret_cast<const u16x8*>(bb.beta + n0 + 8 * c);
@@ -149,10 +165,6 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[TM][2], int wm, i
     if (off < 0) continue;
     u16x8 v = *reinterpret_cast<const u16x8*>(lds + rr * LP + 8 * c);
     if constexpr (EPI == 1) {
-      if (add) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) + bf2f(av[k][e]));
-      }
       if (bwd) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
