@@ -528,6 +528,29 @@ void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y,
 // (seed, sample0 + r, pos[r], token) (sample.hip). pos: int32 [rows] on the device.
 void sample_logits_bf16(const void* logits, int rows, int ld, int vocab, float inv_temp, int top_k,
                         unsigned long long seed, unsigned sample0, const int* pos, int64_t* out, hipStream_t stream);
+// sample_logits' token with top-p and the generation step's bookkeeping in the same launch (sample.hip).
+// top_p outside (0, 1) or temperature == 0: no nucleus. tokens [rows] always gets the row's token. Optional (nullptr:
+// off): out [rows][ld_out] int64 with W columns gets the token at column pos[r]; gen_len [rows] grows by one; done
+// [rows] is set when the token equals eos (-1: none). A row whose done flag is set on entry emits pad and changes
+// nothing; pos[r] outside [0, W) writes neither out, gen_len nor done. thr_out (bf16 [rows], a test hook): write the
+// candidate threshold's logit value there (-inf: no threshold) and draw nothing. vocab <= 2^23.
+struct SampleStepArgs {
+  const void* logits = nullptr;
+  int rows = 0, ld = 0, vocab = 0, top_k = 0;
+  double temperature = 0.0, top_p = 1.0;
+  unsigned long long seed = 0;
+  unsigned sample0 = 0;
+  const int* pos = nullptr;
+  int64_t* tokens = nullptr;
+  int64_t* out = nullptr;
+  long ld_out = 0;
+  int W = 0;
+  int* done = nullptr;
+  int* gen_len = nullptr;
+  int64_t eos = -1, pad = 0;
+  void* thr_out = nullptr;
+};
+void sample_step_bf16(const SampleStepArgs& a, hipStream_t stream);
 // out[r] = bf16(wte[tok[r]] + wpe[pos[r]])  (C % 4 == 0; wte [V][C], wpe [P][C]; pos int32 on the device)
 void embedding_at_bf16(const int64_t* tok, const int* pos, const void* wte, const void* wpe, void* out, int rows, int C,
                        int V, int P, hipStream_t stream);

@@ -2188,6 +2188,80 @@ torch::Tensor sample_logits(torch::Tensor logits, int64_t vocab, double temperat
   return out;
 }
 
+// sample_logits' checks and arguments, shared by sample_step and top_p_threshold
+static sdml::SampleStepArgs sample_step_args(const char* who, const torch::Tensor& logits, int64_t vocab,
+                                             double temperature, int64_t top_k, double top_p, int64_t seed,
+                                             int64_t sample0, const torch::Tensor& pos) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kBFloat16 && logits.dim() == 2 &&
+                  logits.stride(1) == 1 && (logits.size(0) <= 1 || logits.stride(0) >= logits.size(1)),
+              who, ": logits must be a [B, ld] bf16 device tensor with unit column stride");
+  const int64_t B = logits.size(0), ld = B > 1 ? logits.stride(0) : logits.size(1);
+  TORCH_CHECK(vocab >= 1 && vocab <= logits.size(1) && ld <= INT_MAX && vocab <= (1 << 23), who, ": vocab ", vocab,
+              " outside the ", logits.size(1), " columns (or above 2^23)");
+  TORCH_CHECK(temperature >= 0.0 && std::isfinite(temperature), who, ": temperature must be >= 0");
+  TORCH_CHECK(top_p >= 0.0 && top_p <= 1.0, who, ": top_p must be in [0, 1]");
+  TORCH_CHECK(seed >= 0 && sample0 >= 0 && sample0 + B <= (int64_t)UINT32_MAX, who, ": seed / sample0 range");
+  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kInt32 && pos.is_contiguous() && pos.numel() == B &&
+                  pos.device() == logits.device(),
+              who, ": pos must be int32 [B] on the logits' device");
+  const float inv_temp = temperature > 0.0 ? (float)(1.0 / temperature) : 0.f;
+  TORCH_CHECK(temperature == 0.0 || (inv_temp > 0.f && std::isfinite(inv_temp)), who, ": temperature out of range");
+  sdml::SampleStepArgs a;
+  a.logits = logits.data_ptr();
+  a.rows = (int)B, a.ld = (int)ld, a.vocab = (int)vocab;
+  a.top_k = (int)std::max<int64_t>(0, std::min<int64_t>(top_k, vocab));
+  a.temperature = temperature, a.top_p = top_p;
+  a.seed = (unsigned long long)seed, a.sample0 = (unsigned)sample0;
+  a.pos = pos.data_ptr<int>();
+  return a;
+}
+
+// sample_logits with top-p, and the generation step's bookkeeping in the same launch (kernels.h SampleStepArgs).
+// out: int64 [B, W] (unit column stride); done, gen_len: int32 [B]. Returns the step's tokens [B].
+torch::Tensor sample_step(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, double top_p,
+                          int64_t seed, int64_t sample0, torch::Tensor pos, c10::optional<torch::Tensor> out,
+                          c10::optional<torch::Tensor> done, c10::optional<torch::Tensor> gen_len, int64_t eos,
+                          int64_t pad) {
+  auto a = sample_step_args("sample_step", logits, vocab, temperature, top_k, top_p, seed, sample0, pos);
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(eos >= -1 && eos < vocab && pad >= 0 && pad < vocab, "sample_step: eos / pad outside the vocabulary");
+  if (out) {
+    TORCH_CHECK(out->is_cuda() && out->device() == logits.device() && out->scalar_type() == torch::kInt64 &&
+                    out->dim() == 2 && out->size(0) == B && out->size(1) >= 1 && out->size(1) <= INT_MAX &&
+                    out->stride(1) == 1 && (B <= 1 || out->stride(0) >= out->size(1)),
+                "sample_step: out must be an int64 [B, W] device tensor with unit column stride");
+    a.out = out->data_ptr<int64_t>();
+    a.ld_out = B > 1 ? (long)out->stride(0) : (long)out->size(1);
+    a.W = (int)out->size(1);
+  }
+  for (const auto* t : {&done, &gen_len})
+    if (*t)
+      TORCH_CHECK((*t)->is_cuda() && (*t)->device() == logits.device() && (*t)->scalar_type() == torch::kInt32 &&
+                      (*t)->is_contiguous() && (*t)->numel() == B,
+                  "sample_step: done / gen_len must be contiguous int32 [B] device tensors");
+  if (done) a.done = done->data_ptr<int>();
+  if (gen_len) a.gen_len = gen_len->data_ptr<int>();
+  a.eos = eos, a.pad = pad;
+  auto tokens = torch::empty({B}, logits.options().dtype(torch::kInt64));
+  a.tokens = tokens.data_ptr<int64_t>();
+  sdml::sample_step_bf16(a, cur_stream());
+  return tokens;
+}
+
+// the candidate threshold of sample_step as a logit value, bf16 [B] (no threshold: -inf); temperature > 0
+torch::Tensor top_p_threshold(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, double top_p) {
+  const int64_t B = logits.dim() == 2 ? logits.size(0) : 0;
+  auto pos = torch::zeros({B}, logits.options().dtype(torch::kInt32));
+  auto a = sample_step_args("top_p_threshold", logits, vocab, temperature, top_k, top_p, 0, 0, pos);
+  TORCH_CHECK(temperature > 0.0, "top_p_threshold: temperature must be > 0");
+  auto thr = torch::empty({B}, logits.options());
+  auto tokens = torch::empty({B}, logits.options().dtype(torch::kInt64));
+  a.tokens = tokens.data_ptr<int64_t>();
+  a.thr_out = thr.data_ptr();
+  sdml::sample_step_bf16(a, cur_stream());
+  return thr;
+}
+
 // wte[tok[b]] + wpe[pos[b]] -> [B, C] bf16; tok int64 [B], pos int32 [B], both on the device
 torch::Tensor embedding_at(torch::Tensor tok, torch::Tensor pos, torch::Tensor wte, torch::Tensor wpe) {
   TORCH_CHECK(tok.is_cuda() && tok.scalar_type() == torch::kInt64 && tok.is_contiguous() && tok.dim() == 1,
@@ -2221,6 +2295,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_logits", &sample_logits, "greedy / top-k Gumbel-max sampling of bf16 logits rows on the device",
         py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("seed"),
         py::arg("sample0"), py::arg("pos"));
+  m.def("sample_step", &sample_step,
+        "sample_logits with top-p and the step's bookkeeping (token matrix, done flags, lengths) in one launch",
+        py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("seed"), py::arg("sample0"), py::arg("pos"), py::arg("out") = py::none(),
+        py::arg("done") = py::none(), py::arg("gen_len") = py::none(), py::arg("eos") = -1, py::arg("pad") = 0);
+  m.def("top_p_threshold", &top_p_threshold, "the candidate threshold of sample_step as a logit value, bf16 [B]",
+        py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"));
   m.def("embedding_at", &embedding_at, "wte[tok[b]] + wpe[pos[b]] (bf16)");
   m.def("linear_fwd_u8", &linear_fwd_u8, "act(scale * x_u8 @ w.T + b): uint8-pixel first layer", py::arg("x"),
         py::arg("w"), py::arg("b"), py::arg("relu"), py::arg("scale"), py::arg("planes") = py::none(),

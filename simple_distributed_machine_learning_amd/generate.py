@@ -5,10 +5,13 @@
 ``train``). The master prints one line of token ids per sample: the prompt followed by the new tokens, separated by
 commas. There is no tokenizer in this project, so token ids are the interface.
 
-Prompts: ``--prompt_tokens 1,2,3`` (repeatable; all of one length), or ``--prompt_from_data N`` with ``--prompt_len L``
-(the first L tokens of the first N test sequences of the synthetic token data, ``--data_seed`` + 1 as in ``train``).
-``--temperature 0`` (default) is greedy; ``--temperature T --top_k K`` samples with noise keyed by (``--seed``, sample,
-position), see parallel/generate.py. ``--metrics`` gets one ``generate`` event: tokens, seconds, tokens/s.
+Prompts: ``--prompt_tokens 1,2,3`` (repeatable; all of one length unless ``--ragged`` is given), or
+``--prompt_from_data N`` with ``--prompt_len L`` (the first L tokens of the first N test sequences of the synthetic
+token data, ``--data_seed`` + 1 as in ``train``). ``--temperature 0`` (default) is greedy; ``--temperature T --top_k K
+--top_p P`` samples with noise keyed by (``--seed``, sample, position), see parallel/generate.py. ``--eos_token E``
+ends a row after it draws E (``--pad_token`` fills what follows, ``--stop_check N`` is how often the host looks
+whether all rows have ended). With ``--ragged`` or ``--eos_token`` a printed line holds the row's tokens up to its own
+length. ``--metrics`` gets one ``generate`` event: the tokens really generated, seconds, tokens/s.
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ from . import cli
 from .data import SyntheticTokens
 from .models import DEFAULT_STAGES, get_model_spec
 from .parallel import PipelineEngine, init_mesh, shutdown
-from .parallel.generate import generate
+from .parallel.generate import generate, pad_prompts
 from .train import _device
 from .utils.checkpoint import load_checkpoint
 from .utils.metrics import JsonlMetrics
@@ -51,13 +54,20 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--metrics", default=None, help="JSONL metrics file (rank 0)")
     s = p.add_argument_group("generation")
     s.add_argument("--prompt_tokens", action="append", default=None, metavar="1,2,3",
-                   help="one prompt as comma-separated token ids (repeatable; equal lengths)")
+                   help="one prompt as comma-separated token ids (repeatable; equal lengths unless --ragged)")
+    s.add_argument("--ragged", action="store_true", help="permit --prompt_tokens of unequal lengths")
     s.add_argument("--prompt_from_data", type=int, default=0, metavar="N",
                    help="take the prompts from the first N test sequences of the synthetic token data")
     s.add_argument("--prompt_len", type=int, default=1, help="tokens per --prompt_from_data prompt")
     s.add_argument("--max_new_tokens", type=int, default=16)
     s.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
     s.add_argument("--top_k", type=int, default=0, help="sample among the k most likely tokens (0: all)")
+    s.add_argument("--top_p", type=float, default=1.0,
+                   help="sample inside the nucleus holding this share of the (top-k) mass (0 or 1: off)")
+    s.add_argument("--eos_token", type=int, default=None, help="a row ends after it draws this token")
+    s.add_argument("--pad_token", type=int, default=0, help="fills a row after its end")
+    s.add_argument("--stop_check", type=int, default=16,
+                   help="with --eos_token: steps between the host's looks whether all rows ended (0: never)")
     return p
 
 
@@ -79,21 +89,26 @@ def parse_args(argv: Optional[List[str]] = None):
     return args
 
 
-def _prompts(args, spec) -> torch.Tensor:
+def _prompts(args, spec):
+    """(prompts int64 [B, Lmax], prompt lengths or None)."""
     if args.prompt_tokens:
         try:
             rows = [[int(t) for t in p.split(",") if t.strip() != ""] for p in args.prompt_tokens]
         except ValueError:
             raise SystemExit("--prompt_tokens takes comma-separated integers")
-        if len({len(r) for r in rows}) != 1 or not rows[0]:
-            raise SystemExit("--prompt_tokens: all prompts of one call must have the same, non-zero length")
-        t = torch.tensor(rows, dtype=torch.int64)
-        if int(t.min()) < 0 or int(t.max()) >= spec.vocab_size:
+        if not all(rows) or (len({len(r) for r in rows}) != 1 and not args.ragged):
+            raise SystemExit("--prompt_tokens: all prompts of one call must have the same, non-zero length "
+                             "(--ragged permits unequal ones)")
+        if min(min(r) for r in rows) < 0 or max(max(r) for r in rows) >= spec.vocab_size:
             raise SystemExit(f"--prompt_tokens: token ids must be in [0, {spec.vocab_size})")
-        return t
+        if args.ragged:
+            if not 0 <= args.pad_token < spec.vocab_size:
+                raise SystemExit(f"--pad_token must be in [0, {spec.vocab_size})")
+            return pad_prompts(rows, args.pad_token)
+        return torch.tensor(rows, dtype=torch.int64), None
     S = max(args.prompt_len, spec.seq_len or args.seq_len or 64)
     ds = SyntheticTokens(args.prompt_from_data, S, spec.vocab_size, seed=args.data_seed + 1)
-    return ds.inputs(0, args.prompt_from_data)[:, :args.prompt_len].contiguous()
+    return ds.inputs(0, args.prompt_from_data)[:, :args.prompt_len].contiguous(), None
 
 
 def run(args) -> dict:
@@ -115,23 +130,30 @@ def run(args) -> dict:
     engine = PipelineEngine(spec, mesh, schedule_kind=args.schedule, num_microbatches=1, seed=args.seed)
     if args.ckpt_dir:
         load_checkpoint(engine, args.ckpt_dir)
-    prompts = _prompts(args, spec)
+    prompts, plens = _prompts(args, spec)
     metrics = JsonlMetrics(args.metrics if mesh.is_master() else None, mesh.rank)
     try:
         t0 = time.perf_counter()
-        out = generate(engine, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
-                       seed=args.seed)
+        out, lengths = generate(engine, prompts, args.max_new_tokens, temperature=args.temperature,
+                                top_k=args.top_k, seed=args.seed, top_p=args.top_p, prompt_lens=plens,
+                                eos_token=args.eos_token, pad_token=args.pad_token, stop_check=args.stop_check,
+                                return_lengths=True)
         rows = out.cpu().tolist()  # (the read-back ends the timed region)
+        lengths = lengths.cpu().tolist()
         dt_s = time.perf_counter() - t0
     except ValueError as e:  # the refusals (tp, dp, rotate, lengths): their message, not a traceback
         shutdown(mesh)
         raise SystemExit(str(e))
-    n_new = len(rows) * args.max_new_tokens
+    if plens is not None or args.eos_token is not None:  # each row up to its own length
+        rows = [r[:n] for r, n in zip(rows, lengths)]
+    n_prompt = len(rows) * prompts.shape[1] if plens is None else int(plens.sum())
+    n_new = sum(lengths) - n_prompt  # the tokens really generated (the eos included)
     if mesh.is_master():
         for r in rows:
             print(",".join(str(t) for t in r), flush=True)
         metrics.log(event="generate", samples=len(rows), prompt_len=prompts.shape[1], tokens=n_new, seconds=dt_s,
-                    tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k)
+                    tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k,
+                    top_p=args.top_p)
     return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
 
 

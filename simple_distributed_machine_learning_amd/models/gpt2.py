@@ -290,10 +290,16 @@ class GPT2Stage(PipelineStage):
         return linear_decode(y, w if wp is None else wp)
 
     @torch.no_grad()
-    def prefill(self, x, cache: "KVCache"):
+    def prefill(self, x, cache: "KVCache", lens=None):
         """The prompt through this stage: today's forward (flash attention at the prompt length, no dropout) plus the
         copies of every layer's k / v into the cache. x: tokens [B, S0] on stage 0, else [B, S0, C]. Returns the
-        boundary [B, S0, C], or on the last stage the logits [B, ld] of the last position only."""
+        boundary [B, S0, C], or on the last stage the logits [B, ld] of the last position only.
+
+        ``lens`` (int32 [B] on the device, 1 <= lens[b] <= S0, checked by the caller on the host): ragged prompts,
+        right-padded to S0. Causal attention keeps every position < lens[b] independent of the padding, and the cache
+        rows >= lens[b] are never read by the decode attention (each is overwritten before its turn). The cache
+        lengths become ``lens``, ``cache.n`` = S0 bounds the longest row, and the last stage returns the logits of
+        position lens[b] - 1 of each sample (a gather on the device)."""
         if self.stage_id == 0:
             x = embedding(x, self.wte.weight, self.wpe.weight)
         B, S, C = x.shape
@@ -318,13 +324,19 @@ class GPT2Stage(PipelineStage):
                 x = x + m
             else:
                 x, y = add_layer_norm(x, m, nxt)
-        cache.lens.fill_(S)
+        if lens is None:
+            cache.lens.fill_(S)
+        else:
+            cache.lens.copy_(lens)
         cache.n = S
         if not last:
             return x
         if y is None:
             y = self.ln_f(x)
-        return self._head_logits(y[:, -1].contiguous())
+        if lens is None:
+            return self._head_logits(y[:, -1].contiguous())
+        rows = torch.arange(B, device=y.device) * S + (cache.lens.to(torch.int64) - 1)
+        return self._head_logits(y.reshape(B * S, C).index_select(0, rows))
 
     @torch.no_grad()
     def decode_step(self, x, cache: "KVCache"):
@@ -366,8 +378,9 @@ class GPT2Stage(PipelineStage):
 @dataclass
 class KVCache:
     """A stage's generation state: per local layer K and V [B, Smax, H, D]; ``lens`` int32 [B] on the device (keys
-    cached per sample, what the kernels read); ``n`` the same count on the host (all samples advance together), so
-    the bounds are checked without reading the device."""
+    cached per sample, what the kernels read); ``n`` the host's bound on them (the count itself after an equal-length
+    prefill, the longest row's after a ragged one; all samples advance together), so the bounds are checked without
+    reading the device."""
     k: list
     v: list
     lens: torch.Tensor

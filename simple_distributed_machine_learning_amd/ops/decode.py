@@ -91,3 +91,16 @@ def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int,
         return kernels().sample_logits(logits, int(vocab), float(temperature), int(top_k), int(seed), int(sample0),
                                        positions)
     return _ref.sample_logits(logits, vocab, temperature, top_k, seed, sample0, positions)
+
+
+def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float, seed: int, sample0: int, positions,
+                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0):
+    """sample_logits over the top-p nucleus of the top-k candidates, with one generation step's bookkeeping in the
+    same launch (ops/reference.py sample_step is the definition): tokens int64 [B]; ``out`` int64 [B, W] gets the token
+    at column positions[row], ``gen_len`` int32 [B] grows by one, ``done`` int32 [B] is set on ``eos`` (-1: none); a
+    row already done emits ``pad`` and changes nothing. ROCm bf16: the on-device sampler, no host synchronisation."""
+    if _hip_bf16(logits):
+        return kernels().sample_step(logits, int(vocab), float(temperature), int(top_k), float(top_p), int(seed),
+                                     int(sample0), positions, out, done, gen_len, int(eos), int(pad))
+    return _ref.sample_step(logits, vocab, temperature, top_k, top_p, seed, sample0, positions, out, done, gen_len,
+                            eos, pad)

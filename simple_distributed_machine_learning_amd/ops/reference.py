@@ -327,6 +327,37 @@ def top_k_candidates(logits, top_k: int):
     return ok & (z >= kth)
 
 
+def top_p_threshold(logits, top_k: int, top_p: float, temperature: float):
+    """theta [B] float64 of top_p_candidates (top_p off: -inf, i.e. every top-k candidate passes)."""
+    cand = top_k_candidates(logits, top_k)
+    z = torch.where(cand, logits.double(), torch.full_like(logits, -math.inf, dtype=torch.float64))
+    B = z.shape[0]
+    if not 0.0 < top_p < 1.0 or temperature <= 0:
+        return torch.full((B,), -math.inf, dtype=torch.float64, device=z.device)
+    s = z.sort(1, descending=True).values
+    m = s[:, :1]
+    w = torch.exp((s - m) / float(temperature))
+    w = torch.where(s == m, torch.ones_like(w), w)  # (a maximum of +inf: inf - inf)
+    w = torch.where(torch.isnan(w), torch.zeros_like(w), w)  # (a row without candidates)
+    cum = w.cumsum(1)
+    # the first sorted position whose cumulative mass reaches top_p of the total: its value is theta (inside a run of
+    # equal values the run's end reaches it too, and no larger value's run does)
+    first = (cum >= float(top_p) * cum[:, -1:]).to(torch.int8).argmax(1)
+    return s.gather(1, first[:, None])[:, 0]
+
+
+def top_p_candidates(logits, top_k: int, top_p: float, temperature: float):
+    """[B, V] bool, the nucleus inside the top-k candidates C_k, in float64: with m the largest candidate logit and
+    w_v = exp((l_v - m) / T) for v in C_k, theta is the largest logit value x with sum{w_v : l_v >= x} >= top_p *
+    sum{w_v}; the candidates are {v in C_k : l_v >= theta}. Ties at theta are all kept and every token with the maximal
+    logit is a member. top_p <= 0 or >= 1 (or temperature 0): top_k_candidates."""
+    cand = top_k_candidates(logits, top_k)
+    if not 0.0 < top_p < 1.0 or temperature <= 0:
+        return cand
+    theta = top_p_threshold(logits, top_k, top_p, temperature)
+    return cand & (torch.nan_to_num(logits.double(), nan=-math.inf) >= theta[:, None])
+
+
 def _first_argmax(score, cand):
     """Index of the largest score among the candidates, the lowest index on ties (token 0 for a row without any)."""
     s = torch.where(cand, score, torch.full_like(score, -math.inf))
@@ -353,3 +384,40 @@ def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int,
     g = gumbel_from_uniform(sample_uniforms(seed, samples, positions, vocab))
     inv_t = torch.tensor(1.0 / float(temperature), dtype=torch.float32, device=z.device)
     return _first_argmax(zf * inv_t + g, cand)
+
+
+def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float, seed: int, sample0: int, positions,
+                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0):
+    """sample_logits over the nucleus (top_p_candidates) plus one generation step's bookkeeping, in place. Returns the
+    step's tokens [B]. Per row, with pos = positions[row]: a row whose ``done`` flag is set emits ``pad`` and changes
+    nothing; else the token goes to out[row, pos], gen_len[row] grows by one and done[row] is set when the token is
+    ``eos`` (-1: none). A pos outside [0, W) changes none of the three. With top_p off and no bookkeeping tensors the
+    tokens are sample_logits'."""
+    if temperature < 0:
+        raise ValueError(f"temperature must be >= 0, got {temperature}")
+    if not 0.0 <= top_p <= 1.0:
+        raise ValueError(f"top_p must be in [0, 1], got {top_p}")
+    z = logits[:, :vocab]
+    cand = top_p_candidates(z, top_k, top_p, temperature)
+    zf = torch.nan_to_num(z.float(), nan=-math.inf)
+    B = z.shape[0]
+    if temperature == 0:
+        tok = _first_argmax(zf, cand)
+    else:
+        samples = torch.arange(sample0, sample0 + B, dtype=torch.int64, device=z.device)
+        g = gumbel_from_uniform(sample_uniforms(seed, samples, positions, vocab))
+        inv_t = torch.tensor(1.0 / float(temperature), dtype=torch.float32, device=z.device)
+        tok = _first_argmax(zf * inv_t + g, cand)
+    live = torch.ones(B, dtype=torch.bool, device=z.device) if done is None else done == 0
+    tok = torch.where(live, tok, torch.full_like(tok, pad))
+    pos = positions.to(torch.int64)
+    W = out.shape[1] if out is not None else None
+    write = live if W is None else live & (pos >= 0) & (pos < W)
+    if out is not None:
+        rows = torch.arange(B, device=z.device)[write]
+        out[rows, pos[write]] = tok[write]
+    if gen_len is not None:
+        gen_len += write.to(gen_len.dtype)
+    if done is not None:
+        done |= (write & (tok == eos)).to(done.dtype)
+    return tok

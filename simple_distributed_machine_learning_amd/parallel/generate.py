@@ -13,6 +13,13 @@ prompt's row, position = the index of the token drawn. The result does not depen
 or the rank. A decode step reads nothing back from the device: positions live in the cache's device-side lengths and
 the sampled tokens stay on the device until the end.
 
+Ragged prompts, stop tokens and top-p (``prompt_lens``, ``eos_token``, ``top_p`` in (0, 1)) move the step onto
+``sample_step``, which draws the token and, in the same launch, writes it to the token matrix at the row's own position
+(its cache length), counts it and sets the row's done flag on the eos; a done row emits the pad token and writes
+nothing. The result is ``[B, Lmax + max_new_tokens]``: a row's prompt, its generated tokens contiguously from its own
+length, the pad token after. Only with an eos, every ``stop_check`` steps, the host reads one flag (are all rows done?),
+agreed through the pipeline group where there is one. A call without the three arguments runs the lines it always ran.
+
 Limitations: tensor parallelism, data parallelism and ``--schedule rotate`` are refused. With pp ranks one rank works
 at a time (a token must leave the last stage before stage 0 can embed it); several sample groups in flight would fill
 the bubble and are not implemented.
@@ -23,7 +30,7 @@ from typing import Optional
 
 import torch
 
-from ..ops.decode import sample_logits
+from ..ops.decode import sample_logits, sample_step
 
 # message tags no schedule produces: message_tag() keeps mb * 4096 + stage in the bits above 2, and a schedule's
 # stage index is far below 4095
@@ -62,16 +69,58 @@ def _check(engine, prompts, max_new_tokens: int):
     return prompts, cfg
 
 
+def pad_prompts(prompts, pad_token: int = 0):
+    """(tokens int64 [B, Lmax] right-padded with ``pad_token``, lengths int32 [B]) from a list of token-id lists of
+    any non-zero lengths: the ``prompts`` / ``prompt_lens`` pair of a ragged ``generate`` call."""
+    rows = [list(p) for p in prompts]
+    if not rows or not all(rows):
+        raise ValueError("pad_prompts: every prompt needs at least one token")
+    lmax = max(len(r) for r in rows)
+    t = torch.tensor([r + [int(pad_token)] * (lmax - len(r)) for r in rows], dtype=torch.int64)
+    return t, torch.tensor([len(r) for r in rows], dtype=torch.int32)
+
+
+def _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check):
+    """The refusals of the new arguments; returns the prompt lengths as a list (None: one length)."""
+    if not 0.0 <= float(top_p) <= 1.0:
+        raise ValueError(f"generate: top_p must be in [0, 1], got {top_p}")
+    V = cfg.vocab_size
+    if eos_token is not None and not 0 <= int(eos_token) < V:
+        raise ValueError(f"generate: eos_token {eos_token} is outside the vocabulary [0, {V})")
+    if not 0 <= int(pad_token) < V:
+        raise ValueError(f"generate: pad_token {pad_token} is outside the vocabulary [0, {V})")
+    if int(stop_check) < 0:
+        raise ValueError(f"generate: stop_check must be >= 0, got {stop_check}")
+    if prompt_lens is None:
+        return None
+    B, Lmax = prompts.shape
+    lens = [int(v) for v in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+    if len(lens) != B:
+        raise ValueError(f"generate: {len(lens)} prompt_lens for {B} prompts")
+    if min(lens) < 1 or max(lens) > Lmax:
+        raise ValueError(f"generate: prompt_lens must be in 1..{Lmax} (the prompts' width), got {lens}")
+    return lens
+
+
 @torch.no_grad()
 def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
-             seed: Optional[int] = None, sample0: int = 0) -> torch.Tensor:
+             seed: Optional[int] = None, sample0: int = 0, top_p: float = 1.0, prompt_lens=None,
+             eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False):
     """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
-    ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise."""
+    ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
+    samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
+    ``pad_prompts``): ragged prompts, every row generating up to ``max_new_tokens`` tokens from its own length on.
+    ``eos_token``: a row stops after drawing it; what follows is ``pad_token``. ``stop_check``: with an eos, the host
+    asks every that many steps whether all rows are done (0: never; the result does not depend on it).
+    ``return_lengths``: (tokens, lengths int64 [B]), a row's prompt plus its generated tokens, the eos included."""
     from ..models.gpt2 import dropout_seed
 
     prompts, cfg = _check(engine, prompts, int(max_new_tokens))
     if temperature < 0:
         raise ValueError(f"generate: temperature must be >= 0, got {temperature}")
+    lens_host = _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check)
+    # the step kernel (sample + bookkeeping in one launch) serves the new arguments; without them: the lines below
+    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0
     mesh, dev, P = engine.mesh, engine.device, engine.P
     sched = engine.schedule(1, True)
     owner = [sched.stage_rank(0, s) for s in range(P)]  # pipeline rank of each stage
@@ -82,10 +131,21 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     new = int(max_new_tokens)
     total = S0 + new
     prompts = prompts.to(dev)
-    out = torch.empty((B, total), dtype=torch.int64, device=dev)
-    out[:, :S0] = prompts
+    # tokens and, in a last column, the lengths: one buffer, so the final broadcast carries both
+    buf = torch.empty((B, total + 1), dtype=torch.int64, device=dev)
+    out = buf[:, :total]
+    lens0 = torch.tensor(lens_host if lens_host is not None else [S0] * B, dtype=torch.int64, device=dev)
+    if stepped:
+        out.fill_(int(pad_token))
+        out[:, :S0] = torch.where(torch.arange(S0, device=dev)[None, :] < lens0[:, None], prompts,
+                                  torch.full_like(prompts, int(pad_token)))
+        prompts = out[:, :S0].contiguous()  # (the padding holds the pad token, whatever the caller left there)
+    else:
+        out[:, :S0] = prompts
+    buf[:, total] = lens0 if stepped else total
     if new == 0:
-        return out
+        res = out.contiguous()
+        return (res, buf[:, total].clone()) if return_lengths else res
     nseed = dropout_seed(0 if seed is None else seed)
     mine = [s for s in range(P) if owner[s] == me and s in engine.stages]
     was_training = {s: engine.stages[s].training for s in mine}
@@ -95,6 +155,11 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     dt = engine.dtype
     C = cfg.n_embd
     first, last = owner[0], owner[P - 1]
+    lens_dev = lens0.to(torch.int32) if lens_host is not None else None
+    done = torch.zeros(B, dtype=torch.int32, device=dev)
+    gen_len = torch.zeros(B, dtype=torch.int32, device=dev)
+    eos = -1 if eos_token is None else int(eos_token)
+    check = int(stop_check) if eos_token is not None else 0
 
     def run_stages(x, step: int, prefill: bool):
         """Run this rank's stages in order for one prefill / decode step; x: stage 0's input where this rank holds it.
@@ -105,11 +170,16 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
                 continue
             if s > 0 and owner[s - 1] != me:
                 shape = (B, S0, C) if prefill else (B, C)
-                buf = engine.bufs.get(("gen_act", s, prefill), shape, dt)
-                tr.irecv(buf, grank(owner[s - 1]), _tag(PL_GEN_ACT, s, step)).wait()
-                x = buf
+                buf_ = engine.bufs.get(("gen_act", s, prefill), shape, dt)
+                tr.irecv(buf_, grank(owner[s - 1]), _tag(PL_GEN_ACT, s, step)).wait()
+                x = buf_
             mod = engine.stages[s]
-            x = mod.prefill(x, caches[s]) if prefill else mod.decode_step(x, caches[s])
+            if not prefill:
+                x = mod.decode_step(x, caches[s])
+            elif lens_dev is None:
+                x = mod.prefill(x, caches[s])
+            else:
+                x = mod.prefill(x, caches[s], lens=lens_dev)
             if s == P - 1:
                 res = x
             elif owner[s + 1] != me:
@@ -131,28 +201,46 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
             tr.isend(tok, grank(first), _tag(PL_GEN_TOK, 0, step))
             return tok
         if me == first:
-            buf = engine.bufs.get(("gen_tok",), (B,), torch.int64)
-            tr.irecv(buf, grank(last), _tag(PL_GEN_TOK, 0, step)).wait()
-            return buf
+            buf_ = engine.bufs.get(("gen_tok",), (B,), torch.int64)
+            tr.irecv(buf_, grank(last), _tag(PL_GEN_TOK, 0, step)).wait()
+            return buf_
         return None
+
+    def all_done() -> bool:
+        """The one host read of the stop check: are all rows done? The last stage's rank holds the flags; in a
+        pipeline every rank learns the answer through the pipeline group (the others add zeros)."""
+        if mesh.pp == 1 or tr is None:
+            return bool(done.min().item())
+        flag = done.min().to(torch.int64).reshape(1) if me == last else torch.zeros(1, dtype=torch.int64, device=dev)
+        tr.all_reduce(flag, channel="fwd", async_op=False)
+        return bool(flag.item())
 
     try:
         tok = None
-        for t in range(new):  # token index S0 + t
+        for t in range(new):  # token index S0 + t (ragged: lens[b] + t)
             x = (prompts if t == 0 else tok) if me == first else None
             logits = run_stages(x, t, prefill=(t == 0))
             if me == last:
                 cache = caches[P - 1]
-                tok = sample_logits(logits, cfg.vocab_size, temperature, top_k, nseed, sample0, cache.lens)
-                out[:, S0 + t] = tok
+                if stepped:
+                    tok = sample_step(logits, cfg.vocab_size, temperature, top_k, top_p, nseed, sample0, cache.lens,
+                                      out, done, gen_len, eos, int(pad_token))
+                else:
+                    tok = sample_logits(logits, cfg.vocab_size, temperature, top_k, nseed, sample0, cache.lens)
+                    out[:, S0 + t] = tok
+            if check and (t + 1) % check == 0 and t + 1 < new and all_done():
+                break
             if t + 1 < new:
                 tok = exchange_token(tok, t)
+        if stepped and me == last:
+            buf[:, total] = lens0 + gen_len
         if tr is not None:
             tr.drain_sends()
             if mesh.pp > 1:  # the last stage's rank holds the tokens: everyone gets them
-                mask = out if me == last else out.zero_()
+                mask = buf if me == last else buf.zero_()
                 tr.all_reduce(mask, channel="fwd", async_op=False)
     finally:
         for s in mine:
             engine.stages[s].train(was_training[s])
-    return out
+    res = out.contiguous()
+    return (res, buf[:, total].clone()) if return_lengths else res

@@ -3,6 +3,7 @@ whole decode loop, hand-written against library-substituted, alternated in one p
 
     python tools/bench_generate.py [--B 16] [--ctx 512] [--rounds 3] [--sweep]
         [--out_kernels profiles/generate_kernels.jsonl] [--out_loop profiles/generate_gpt2.jsonl]
+    python tools/bench_generate.py --ragged [--out_ragged profiles/ragged_generate.jsonl]
 
 Per kernel (one JSON line per kernel, shape and round): the time of one call, taken as a device-event window around
 --reps back-to-back calls, and the achieved GB/s of the bytes that must move: W for the projections (x and y are
@@ -18,6 +19,14 @@ greedy sampling on the device, tokens/s = B * steps / seconds (host clock around
 same loop with torch.addmm, index_put + scaled_dot_product_attention, F.embedding and argmax in place of the four
 hand kernels (the LayerNorm kernels are the same in both). The gate: hand >= lib at --B 16 --ctx 512.
 --sweep adds B in {1, 16, 64} x ctx in {128, 1024}.
+
+--ragged measures only the step sampler (sample_step: top-p and the step's bookkeeping) and writes --out_ragged:
+  * the sampler window, --reps back-to-back calls on logits [B, 50257] (ld 50304) at T = 0.8, alternated over --rounds:
+    sample_step at top_p = 0.9 with top_k 0 and 50, against (a) sample_logits (top_p off) and (b) top-p in torch (sort,
+    softmax, cumsum, Gumbel-max) on the same logits. The gate: sample_step is not slower than (b); the cost over (a) is
+    reported only.
+  * one decode-loop row: the loop with ragged cache lengths and sample_step doing the bookkeeping (token matrix, done
+    flags, lengths, an eos set) against today's loop (sample_logits and the column store out[:, t] = tok).
 """
 import argparse
 import json
@@ -32,7 +41,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from simple_distributed_machine_learning_amd import _native  # noqa: E402
 from simple_distributed_machine_learning_amd.models import get_model_spec  # noqa: E402
-from simple_distributed_machine_learning_amd.ops.decode import sample_logits  # noqa: E402
+from simple_distributed_machine_learning_amd.ops.decode import sample_logits, sample_step  # noqa: E402
 from simple_distributed_machine_learning_amd.ops.transformer import add_layer_norm, layer_norm_pass  # noqa: E402
 from simple_distributed_machine_learning_amd.parallel import PipelineEngine, init_mesh  # noqa: E402
 
@@ -162,6 +171,100 @@ def run_loop(engine, B, ctx, steps, hand):
     return time.perf_counter() - t0
 
 
+# ---- the step sampler (--ragged) -----------------------------------------------------------------------------------
+def torch_top_p(z, V, T, top_k, top_p):
+    """Top-p sampling in library calls: sort, softmax, cumsum, Gumbel-max over the kept prefix."""
+    l = z[:, :V].float() / T
+    if top_k:
+        l = l.masked_fill(l < l.topk(top_k).values[:, -1:], -float("inf"))
+    s, idx = l.sort(descending=True)
+    pr = s.softmax(-1)
+    s = s.masked_fill(pr.cumsum(-1) - pr >= top_p, -float("inf"))  # drop what follows the token that reaches top_p
+    g = -torch.log(-torch.log(torch.rand_like(s).clamp_(1e-7, 1 - 1e-7)))
+    return idx.gather(1, (s + g).argmax(-1, keepdim=True))[:, 0]
+
+
+def bench_sampler(B, rounds, reps, emit):
+    V, ld, T, P = 50257, 50304, 0.8, 0.9
+    z = torch.zeros(B, ld, device=DEV, dtype=BF)
+    z[:, :V] = (torch.randn(B, V, device=DEV) * 2.0).to(BF)
+    pos = torch.arange(B, dtype=torch.int32, device=DEV)
+    ok = True
+    for top_k in (0, 50):
+        fns = {"sample_step top_p": lambda i: sample_step(z, V, T, top_k, P, 1, 0, pos),
+               "sample_logits": lambda i: sample_logits(z, V, T, top_k, 1, 0, pos),
+               "torch top_p": lambda i: torch_top_p(z, V, T, top_k, P)}
+        for fn in fns.values():
+            window(fn, 10)
+        us = {k: [] for k in fns}
+        for r in range(rounds):
+            for kname, fn in fns.items():  # alternated
+                ms = window(fn, reps)
+                us[kname].append(ms * 1e3)
+                emit({"sampler": kname, "B": B, "V": V, "T": T, "top_k": top_k, "top_p": P if "top_p" in kname else 1.0,
+                      "round": r, "us": round(ms * 1e3, 2)})
+        med = {k: statistics.median(v) for k, v in us.items()}
+        gate = med["sample_step top_p"] <= med["torch top_p"]
+        ok = ok and gate
+        emit({"summary": "sampler", "top_k": top_k, "sample_step_us": round(med["sample_step top_p"], 2),
+              "sample_logits_us": round(med["sample_logits"], 2), "torch_top_p_us": round(med["torch top_p"], 2),
+              "step_over_sample_logits": round(med["sample_step top_p"] / med["sample_logits"], 3),
+              "gate_step_not_slower_than_torch": bool(gate)})
+    return ok
+
+
+@torch.no_grad()
+def run_step_loop(engine, B, ctx, steps, ragged):
+    """run_loop with generate()'s sampling lines: today's (sample_logits, then the column store) or, ragged, cache
+    lengths ctx - 3 b and sample_step with the token matrix, the done flags, the lengths and an eos in its launch.
+    Returns (seconds, rows done at the end)."""
+    stages = [engine.stages[s] for s in range(engine.P)]
+    ctx = min(ctx, stages[0].cfg.block_size - steps)
+    caches = [st.new_cache(B, ctx + steps) for st in stages]
+    lens = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+    if ragged:
+        lens -= (3 * torch.arange(B, device=DEV, dtype=torch.int32)).clamp_(max=ctx - 1)
+    for c in caches:
+        for t in c.k + c.v:
+            t.normal_()
+        c.lens.copy_(lens)
+        c.n = ctx
+    V = stages[0].cfg.vocab_size
+    out = torch.zeros((B, ctx + steps), dtype=torch.int64, device=DEV)
+    done = torch.zeros(B, dtype=torch.int32, device=DEV)
+    gen_len = torch.zeros(B, dtype=torch.int32, device=DEV)
+    tok = torch.randint(0, V, (B,), device=DEV)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for t in range(steps):
+        x = tok
+        for st, c in zip(stages, caches):
+            x = st.decode_step(x, c)
+        if ragged:
+            tok = sample_step(x, V, 0.0, 0, 1.0, 0, 0, caches[-1].lens, out, done, gen_len, V - 1, 0)
+        else:
+            tok = sample_logits(x, V, 0.0, 0, 0, 0, caches[-1].lens)
+            out[:, ctx + t] = tok
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, int(done.sum())
+
+
+def bench_step_loop(engine, B, ctx, steps, rounds, emit):
+    for ragged in (False, True):
+        run_step_loop(engine, B, ctx, 8, ragged)
+    tps = {False: [], True: []}
+    for r in range(rounds):
+        for ragged in (False, True):  # alternated
+            s, nd = run_step_loop(engine, B, ctx, steps, ragged)
+            tps[ragged].append(B * steps / s)
+            emit({"loop": "ragged + eos (sample_step)" if ragged else "today (sample_logits + store)", "B": B,
+                  "ctx": ctx, "steps": steps, "round": r, "ms_per_step": round(s / steps * 1e3, 4),
+                  "tokens_per_s": round(B * steps / s, 1), "rows_done": nd})
+    a, b = statistics.median(tps[True]), statistics.median(tps[False])
+    emit({"summary": "decode loop, step sampler", "B": B, "ctx": ctx, "ragged_tokens_per_s": round(a, 1),
+          "today_tokens_per_s": round(b, 1), "ragged_over_today": round(a / b, 3)})
+
+
 def bench_loop(engine, B, ctx, steps, rounds, emit, gate):
     for hand in (True, False):
         run_loop(engine, B, ctx, 8, hand)  # warm-up of both paths at this shape
@@ -192,9 +295,26 @@ def main():
     ap.add_argument("--no_kernels", action="store_true")
     ap.add_argument("--out_kernels", default="profiles/generate_kernels.jsonl")
     ap.add_argument("--out_loop", default="profiles/generate_gpt2.jsonl")
+    ap.add_argument("--ragged", action="store_true", help="only the step sampler's window and its decode-loop row")
+    ap.add_argument("--out_ragged", default="profiles/ragged_generate.jsonl")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py measures on the GPU; none is visible")
+    if a.ragged:
+        os.makedirs(os.path.dirname(a.out_ragged) or ".", exist_ok=True)
+        with open(a.out_ragged, "w") as f:
+            def emit(rec):
+                line = json.dumps(rec)
+                print(line, flush=True)
+                f.write(line + "\n")
+                f.flush()
+
+            ok = bench_sampler(a.B, a.rounds, a.reps, emit)
+            mesh = init_mesh(pp=1, schedule_kind="1f1b", rank=0, world_size=1, device=DEV)
+            engine = PipelineEngine(get_model_spec("gpt2", 2), mesh, schedule_kind="1f1b", num_microbatches=1)
+            engine.eval()
+            bench_step_loop(engine, a.B, a.ctx, a.steps, a.rounds, emit)
+        return 0 if ok else 1
     for p in (a.out_kernels, a.out_loop):
         os.makedirs(os.path.dirname(p) or ".", exist_ok=True)
     ok = True
