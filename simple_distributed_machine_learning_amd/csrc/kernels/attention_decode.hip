@@ -13,6 +13,11 @@
 // (max, sum, partial O) in chunk order. No atomics. A sample's result depends on its own row of qkv, its own cache
 // rows and lens[b] only: the same bits on every run, in any batch.
 //
+// One-launch form (tickets): a row has nc = lens[b] / CH + 1 live chunks, known on the device. Each stores its slot
+// write-through, draws a ticket on the (b, h) counter, and the wave that draws nc - 1 acquires at agent scope and runs
+// the same combine in the same chunk order (handoff.h): the same bits, no second launch, and the grid may cover Smax.
+// Nothing waits on a counter.
+//
 // Keys past lens[b] never reach the result: their loads are redirected to the new token's own row (so nothing is read
 // from cache rows >= lens[b], which may hold anything), their scores and probabilities are selected away, not
 // multiplied by zero. The chunk that contains index lens[b] owns the cache write, and takes that key from qkv, so no
@@ -22,6 +27,7 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
+#include "handoff.h"
 #include "kernels.h"
 #include "wave_ops.h"
 
@@ -47,8 +53,65 @@ __device__ __forceinline__ u16 f2bf(float f) {
 __device__ __forceinline__ float sum_groups(float x) { return wv::sum_rows(x + wv::dpp<ROR8>(x)); }
 __device__ __forceinline__ float max_groups(float x) { return wv::max_rows(fmaxf(x, wv::dpp<ROR8>(x))); }
 
+// lane = channel: the nc chunks of one (b, h) in chunk order
+__device__ __forceinline__ void combine_chunks(const AttnDecodeArgs& p, int b, int h, int nc, int lane) {
+  const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks;
+  float M = -INFINITY;
+  for (int c = 0; c < nc; ++c) M = fmaxf(M, p.ws_ml[(slot + c) * 2]);
+  float L = 0.f, O = 0.f;
+  for (int c = 0; c < nc; ++c) {
+    const float w = __builtin_amdgcn_exp2f(p.ws_ml[(slot + c) * 2] - M);
+    L = fmaf(p.ws_ml[(slot + c) * 2 + 1], w, L);
+    O = fmaf(p.ws_o[(slot + c) * 64 + lane], w, O);
+  }
+  static_cast<u16*>(p.out)[(int64_t)b * p.H * 64 + h * 64 + lane] = f2bf(O / L);
+}
+
+__device__ __forceinline__ float lane_value(float x, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
+}
+
+// combine_chunks for slots that other workgroups wrote in this launch, behind the caller's acquire: every load of
+// them bypasses the L1 (handoff.h), and since such a load is a round trip to the L2 or beyond, none depends on another. Lane c fetches
+// chunk c's (m, l) and computes its weight, the partial outputs are fetched eight chunks at a time; each lane then
+// runs combine_chunks' fmaf chain in chunk order on the same operands (the max is exact in any order): the same bits.
+__device__ __forceinline__ void combine_handed_off(const AttnDecodeArgs& p, int b, int h, int nc, int lane) {
+  const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks;
+  const float* ml = p.ws_ml + slot * 2;
+  const float* po = p.ws_o + slot * 64 + lane;
+  float m0 = -INFINITY, l0 = 0.f;  // chunk `lane`
+  if (lane < nc) handoff::ld_sc1_x2(ml + 2 * lane, m0, l0);
+  float M = m0;
+  for (int c = 64 + lane; c < nc; c += 64) M = fmaxf(M, handoff::ld_sc1(ml + 2 * c));
+  M = wv::max64(M);
+  float L = 0.f, O = 0.f;
+  for (int c0 = 0; c0 < nc; c0 += 64) {
+    float mc = m0, lc = l0;  // chunk c0 + lane
+    if (c0 > 0) {
+      mc = -INFINITY, lc = 0.f;
+      if (c0 + lane < nc) handoff::ld_sc1_x2(ml + 2 * (c0 + lane), mc, lc);
+    }
+    const float w = __builtin_amdgcn_exp2f(mc - M);
+    const int n = min(64, nc - c0);
+    for (int j0 = 0; j0 < n; j0 += 8) {
+      float o[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = handoff::ld_sc1(po + (int64_t)(c0 + min(j0 + j, n - 1)) * 64);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j0 + j < n) {
+          const float wj = lane_value(w, j0 + j);
+          L = fmaf(lane_value(lc, j0 + j), wj, L);
+          O = fmaf(o[j], wj, O);
+        }
+    }
+  }
+  static_cast<u16*>(p.out)[(int64_t)b * p.H * 64 + h * 64 + lane] = f2bf(O / L);
+}
+
 // grid (chunks, H, B), one wave per block. Lane l: piece l & 7 (channels 8 (l & 7) ..), row group l >> 3; its keys
-// are chunk * CH + 8 i + (l >> 3), i = 0 .. RPL - 1.
+// are chunk * CH + 8 i + (l >> 3), i = 0 .. RPL - 1. TK: the one-launch form.
+template <bool TK>
 __global__ void __launch_bounds__(64) attn_decode_chunk_kernel(AttnDecodeArgs p) {
   const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
   const int len = p.lens[b];
@@ -118,14 +181,30 @@ __global__ void __launch_bounds__(64) attn_decode_chunk_kernel(AttnDecodeArgs p)
   for (int e = 0; e < 8; ++e) o[e] = sum_groups(o[e]);
 
   const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks + c;
-  if (lane < 8) {
-    f32x4* dst = reinterpret_cast<f32x4*>(p.ws_o + slot * 64 + 8 * pc);
-    dst[0] = f32x4{o[0], o[1], o[2], o[3]};
-    dst[1] = f32x4{o[4], o[5], o[6], o[7]};
-  }
-  if (lane == 0) {
-    p.ws_ml[slot * 2] = m;
-    p.ws_ml[slot * 2 + 1] = l;
+  if constexpr (TK) {
+    if (lane < 8) {
+      float* dst = p.ws_o + slot * 64 + 8 * pc;
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) handoff::st_sc1_x2(dst + e, o[e], o[e + 1]);
+    }
+    if (lane == 0) handoff::st_sc1_x2(p.ws_ml + slot * 2, m, l);
+    // the slot went out write-through; draw a ticket on (b, h): the drawer of the last live chunk's combines
+    int* counter = p.tickets + (int64_t)b * p.H + h;
+    const bool mine = handoff::draw_ticket(counter) == len / CH;  // (lane 0's answer counts)
+    handoff::acquire_partials(mine);  // one wave: the drawing lane's wait orders the wave's loads
+    if (!__builtin_amdgcn_readfirstlane(mine)) return;
+    combine_handed_off(p, b, h, len / CH + 1, lane);
+    if (lane == 0) handoff::reset_ticket(counter);
+  } else {
+    if (lane < 8) {
+      f32x4* dst = reinterpret_cast<f32x4*>(p.ws_o + slot * 64 + 8 * pc);
+      dst[0] = f32x4{o[0], o[1], o[2], o[3]};
+      dst[1] = f32x4{o[4], o[5], o[6], o[7]};
+    }
+    if (lane == 0) {
+      p.ws_ml[slot * 2] = m;
+      p.ws_ml[slot * 2 + 1] = l;
+    }
   }
 }
 
@@ -136,16 +215,7 @@ __global__ void __launch_bounds__(64) attn_decode_combine_kernel(AttnDecodeArgs 
   if (len < 0 || len >= p.Smax) return;
   const int nc = len / CH + 1;  // <= max_chunks: the host checked lens[b] + 1 <= n_keys
   if (nc > p.max_chunks) return;
-  const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks;
-  float M = -INFINITY;
-  for (int c = 0; c < nc; ++c) M = fmaxf(M, p.ws_ml[(slot + c) * 2]);
-  float L = 0.f, O = 0.f;
-  for (int c = 0; c < nc; ++c) {
-    const float w = __builtin_amdgcn_exp2f(p.ws_ml[(slot + c) * 2] - M);
-    L = fmaf(p.ws_ml[(slot + c) * 2 + 1], w, L);
-    O = fmaf(p.ws_o[(slot + c) * 64 + lane], w, O);
-  }
-  static_cast<u16*>(p.out)[(int64_t)b * p.H * 64 + h * 64 + lane] = f2bf(O / L);
+  combine_chunks(p, b, h, nc, lane);
 }
 
 }  // namespace
@@ -154,7 +224,11 @@ int attention_decode_chunks(int n_keys) { return (n_keys + CH - 1) / CH; }
 
 void attention_decode_bf16(const AttnDecodeArgs& a, hipStream_t stream) {
   if (a.B <= 0 || a.H <= 0 || a.max_chunks <= 0) return;
-  hipLaunchKernelGGL(attn_decode_chunk_kernel, dim3(a.max_chunks, a.H, a.B), dim3(64), 0, stream, a);
+  if (a.tickets != nullptr) {  // one launch: the last live chunk of a (b, h) to arrive combines
+    hipLaunchKernelGGL(attn_decode_chunk_kernel<true>, dim3(a.max_chunks, a.H, a.B), dim3(64), 0, stream, a);
+    return;
+  }
+  hipLaunchKernelGGL(attn_decode_chunk_kernel<false>, dim3(a.max_chunks, a.H, a.B), dim3(64), 0, stream, a);
   hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(a.H, a.B), dim3(64), 0, stream, a);
 }
 

@@ -501,12 +501,18 @@ void attention_bwd_bf16(const AttnShape& s, hipStream_t stream);
 // the new k, v to cache row lens[b] and out [B][C] = softmax(q K[0..lens[b]]^T scale) V[0..lens[b]]. lens is not
 // changed. The host guarantees lens[b] + 1 <= n_keys <= Smax; max_chunks = attention_decode_chunks(n_keys).
 // ws_ml: [B][H][max_chunks][2] fp32, ws_o: [B][H][max_chunks][64] fp32.
+// tickets (optional, [B][H] int32, zero on entry, left zero): the one-launch form. Each live chunk of (b, h) publishes
+// its slot and draws a ticket; the drawer of the last one runs the combine, so no second launch follows and n_keys may
+// be Smax (the grid need not fit the rows). The same bits as the two-launch form at any n_keys > max(lens). With
+// n_keys <= lens[b] (a violated bound, which the host cannot check) fewer than nc chunks run for that row: its
+// output is not written and its counters are left non-zero.
 constexpr int kAttnDecodeChunk = 64;  // keys per wave: a compile-time constant, not derived from the batch
 struct AttnDecodeArgs {
   const void* qkv = nullptr;
   void *k_cache = nullptr, *v_cache = nullptr, *out = nullptr;
   const int* lens = nullptr;
   float *ws_ml = nullptr, *ws_o = nullptr;
+  int* tickets = nullptr;
   int B = 0, H = 0, Smax = 0, max_chunks = 0;
   long ldq = 0, sb = 0, ss = 0, sh = 0;
   float scale = 1.f;
@@ -516,13 +522,15 @@ void attention_decode_bf16(const AttnDecodeArgs& a, hipStream_t stream);
 // y[M][N] = x[M][K] W[N][K]^T with epi EPI_STORE, EPI_BIAS or EPI_BIAS_GELU (bias [N] bf16); 1 <= M <=
 // kLinearDecodeMaxM, K % 64 == 0, N % 16 == 0, leading dimensions % 8 == 0, 16-B aligned operands, y contiguous.
 // ws: linear_decode_workspace_floats(M, N, K) fp32 (0: none). Deterministic; a row's bits do not depend on M.
+// tickets (optional, N / 16 int32, zero on entry, left zero): with K splits, the split that draws a column tile's last
+// ticket sums the tile's slabs in split order and stores y, so no reduce launch follows. The same bits either way.
 constexpr int kLinearDecodeMaxM = 64;
 constexpr int kLinearDecodeMinBlocks = 256;  // workgroups a shape is split into where K allows (the CU count)
 bool linear_decode_supported(int M, int N, int K, int ldx, int ldw);
 int linear_decode_splits(int N, int K);
 size_t linear_decode_workspace_floats(int M, int N, int K);
 void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y, float* ws, int M, int N, int K,
-                        int ldx, int ldw, int epi, hipStream_t stream);
+                        int ldx, int ldw, int epi, hipStream_t stream, int* tickets = nullptr);
 // out[r] (int64) = the token of row r of bf16 logits [rows][ld] among columns < vocab: inv_temp == 0 greedy, else
 // Gumbel-max at 1 / T = inv_temp over the top_k candidates (top_k <= 0 or >= vocab: all), noise keyed by
 // (seed, sample0 + r, pos[r], token) (sample.hip). pos: int32 [rows] on the device.

@@ -16,11 +16,16 @@
 //     of N and K only). The waves' accumulators are summed through LDS in wave order; with KS > 1 the fp32 partials
 //     go to a workspace and a second launch sums them in split order. No atomics: the same bits on every run, and a
 //     row's result does not depend on M.
+//   * One-launch form (tickets): the splits of a column tile store their slabs write-through, each draws a ticket
+//     on the tile's counter, and the block that draws the last one acquires at agent scope and runs the reduce for
+//     its tile (handoff.h): the same additions in the same order, so the same bits, without the second launch. Nothing
+//     waits on a counter.
 //   * Epilogues: none, bias, bias + GELU; U = bf16(acc + b), y = bf16(gelu(U)), the unfused pair's bits (gelu.h).
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
 #include "gelu.h"
+#include "handoff.h"
 #include "kernels.h"
 
 namespace sdml {
@@ -44,6 +49,7 @@ struct LdParams {
   const u16* bias;
   u16* y;
   float* ws;  // [KS][M][N] fp32 (KS > 1)
+  int* tickets;  // [N / 16] arrival counters of the one-launch form, zero between launches (nullptr: two launches)
   int M, N, K, ldx, ldw;
   int KS, kb_per_split, waves;
   int epi;  // EPI_STORE, EPI_BIAS, EPI_BIAS_GELU
@@ -55,8 +61,8 @@ __device__ __forceinline__ u16 epilogue(float acc, const u16* bias, int n, int e
   return epi == EPI_BIAS ? u : f2bf(gelu_f(bf2f(u)));
 }
 
-// grid (N / 16, KS); block 64 * waves. MG = ceil(M / 16) row groups.
-template <int MG>
+// grid (N / 16, KS); block 64 * waves. MG = ceil(M / 16) row groups. TK: the one-launch form (KS > 1 and tickets).
+template <int MG, bool TK>
 __global__ void __launch_bounds__(64 * MAXW) linear_decode_kernel(LdParams p) {
   __shared__ float red[MAXW][MG * 16][17];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -104,10 +110,43 @@ __global__ void __launch_bounds__(64 * MAXW) linear_decode_kernel(LdParams p) {
     if (m >= p.M) continue;
     float s = red[0][m][n];
     for (int w = 1; w < p.waves; ++w) s += red[w][m][n];
-    if (p.KS > 1)
+    if (TK)
+      handoff::st_sc1(&p.ws[((int64_t)blockIdx.y * p.M + m) * p.N + n0 + n], s);
+    else if (p.KS > 1)
       p.ws[((int64_t)blockIdx.y * p.M + m) * p.N + n0 + n] = s;
     else
       p.y[(int64_t)m * p.N + n0 + n] = epilogue(s, p.bias, n0 + n, p.epi);
+  }
+  if constexpr (TK) {
+    // the slab went out write-through; draw a ticket on the tile (handoff.h). red is free after the barrier inside
+    // draw_ticket and carries "this workgroup drew the last one" to every wave.
+    const int t = handoff::draw_ticket(p.tickets + blockIdx.x);
+    handoff::acquire_partials(t == p.KS - 1);
+    if (threadIdx.x == 0) red[0][0][0] = t == p.KS - 1 ? 1.f : 0.f;
+    __syncthreads();
+    if (red[0][0][0] == 0.f) return;
+    // linear_decode_reduce_kernel's sum for this tile, the splits in split order; 2 columns per thread
+    const int64_t slab = (int64_t)p.M * p.N;
+    for (int e = threadIdx.x; e < MG * 16 * 8; e += blockDim.x) {
+      const int m = e >> 3, n = n0 + 2 * (e & 7);
+      if (m >= p.M) continue;
+      const int64_t i = (int64_t)m * p.N + n;
+      float s0, s1;
+      handoff::ld_sc1_x2(p.ws + i, s0, s1);
+      for (int k = 1; k < p.KS; k += 4) {  // (four slabs' loads in flight: each is a round trip past the L1)
+        float a0[4], a1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) handoff::ld_sc1_x2(p.ws + slab * min(k + j, p.KS - 1) + i, a0[j], a1[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (k + j < p.KS) s0 += a0[j], s1 += a1[j];
+      }
+      typedef u16 u16x2 __attribute__((ext_vector_type(2)));
+      u16x2 o;
+      o[0] = epilogue(s0, p.bias, n, p.epi), o[1] = epilogue(s1, p.bias, n + 1, p.epi);
+      *reinterpret_cast<u16x2*>(p.y + i) = o;
+    }
+    if (threadIdx.x == 0) handoff::reset_ticket(p.tickets + blockIdx.x);
   }
 }
 
@@ -147,7 +186,7 @@ size_t linear_decode_workspace_floats(int M, int N, int K) {
 }
 
 void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y, float* ws, int M, int N, int K,
-                        int ldx, int ldw, int epi, hipStream_t stream) {
+                        int ldx, int ldw, int epi, hipStream_t stream, int* tickets) {
   LdParams p;
   p.x = static_cast<const u16*>(x);
   p.w = static_cast<const u16*>(w);
@@ -159,12 +198,22 @@ void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y,
   p.kb_per_split = (K / 64) / p.KS;
   p.waves = p.kb_per_split < MAXW ? p.kb_per_split : MAXW;
   p.epi = epi;
+  p.tickets = p.KS > 1 ? tickets : nullptr;
   const dim3 grid(N / 16, p.KS), block(64 * p.waves);
+  if (p.tickets != nullptr) {  // one launch: the last split to arrive at a tile reduces it
+    switch ((M + 15) / 16) {
+      case 1: hipLaunchKernelGGL((linear_decode_kernel<1, true>), grid, block, 0, stream, p); break;
+      case 2: hipLaunchKernelGGL((linear_decode_kernel<2, true>), grid, block, 0, stream, p); break;
+      case 3: hipLaunchKernelGGL((linear_decode_kernel<3, true>), grid, block, 0, stream, p); break;
+      default: hipLaunchKernelGGL((linear_decode_kernel<4, true>), grid, block, 0, stream, p); break;
+    }
+    return;
+  }
   switch ((M + 15) / 16) {
-    case 1: hipLaunchKernelGGL(linear_decode_kernel<1>, grid, block, 0, stream, p); break;
-    case 2: hipLaunchKernelGGL(linear_decode_kernel<2>, grid, block, 0, stream, p); break;
-    case 3: hipLaunchKernelGGL(linear_decode_kernel<3>, grid, block, 0, stream, p); break;
-    default: hipLaunchKernelGGL(linear_decode_kernel<4>, grid, block, 0, stream, p); break;
+    case 1: hipLaunchKernelGGL((linear_decode_kernel<1, false>), grid, block, 0, stream, p); break;
+    case 2: hipLaunchKernelGGL((linear_decode_kernel<2, false>), grid, block, 0, stream, p); break;
+    case 3: hipLaunchKernelGGL((linear_decode_kernel<3, false>), grid, block, 0, stream, p); break;
+    default: hipLaunchKernelGGL((linear_decode_kernel<4, false>), grid, block, 0, stream, p); break;
   }
   if (p.KS > 1) {
     const int64_t n4 = (int64_t)M * N / 4;

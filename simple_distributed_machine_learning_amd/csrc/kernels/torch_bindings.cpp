@@ -2089,12 +2089,25 @@ void stream_wait_value32(int64_t ptr, int64_t value) {
 }
 
 // ---- generation (attention_decode.hip, linear_decode.hip, sample.hip) ----------------------------------------------
+// the optional counters of the one-launch forms (kernels.h): int32 on the operands' device, at least `need` entries
+static int* decode_tickets(const char* who, const c10::optional<torch::Tensor>& tickets, const torch::Tensor& like,
+                           int64_t need, const char* unit) {
+  if (!tickets.has_value() || !tickets->defined()) return nullptr;
+  TORCH_CHECK(tickets->is_cuda() && tickets->device() == like.device(), who,
+              ": tickets must be on the operands' device, got ", tickets->device());
+  TORCH_CHECK(tickets->scalar_type() == torch::kInt32 && tickets->is_contiguous(), who,
+              ": tickets must be a contiguous int32 tensor, got ", tickets->scalar_type());
+  TORCH_CHECK(tickets->numel() >= need, who, ": ", tickets->numel(), " tickets, but ", need, " are needed (", unit, ")");
+  return tickets->data_ptr<int>();
+}
+
 // qkv [B, 3C] (the new token's fused projection), k_cache / v_cache [B, Smax, H, 64] views (any strides that are
 // multiples of 8 with contiguous channels, the same for both), lens int32 [B]: keys already cached. n_keys: the
 // host's bound lens[b] + 1 <= n_keys (it advances the lengths itself, so it knows them without reading the device).
-// Writes the new k, v at cache row lens[b]; returns the attention output [B, C].
+// Writes the new k, v at cache row lens[b]; returns the attention output [B, C]. tickets: the one-launch form
+// (kernels.h), at least B * H int32 zeros on the device, left zero.
 torch::Tensor attention_decode(torch::Tensor qkv, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor lens,
-                               double scale, int64_t n_keys) {
+                               double scale, int64_t n_keys, c10::optional<torch::Tensor> tickets) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1,
               "attention_decode: qkv must be a [B, 3C] bf16 device tensor with unit column stride");
   TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.scalar_type() == torch::kBFloat16 &&
@@ -2117,6 +2130,7 @@ torch::Tensor attention_decode(torch::Tensor qkv, torch::Tensor k_cache, torch::
               Smax, " rows (lens[b] + 1 <= n_keys <= Smax)");
   TORCH_CHECK(B >= 1 && B <= 65535 && H <= 65535, "attention_decode: batch / heads out of the grid's range");
   sdml::AttnDecodeArgs a;
+  a.tickets = decode_tickets("attention_decode", tickets, qkv, B * H, "one per sample and head");
   a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
   auto out = torch::empty({B, C}, qkv.options());
   auto ws = torch::empty({B * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
@@ -2137,7 +2151,9 @@ bool linear_decode_supported_op(int64_t M, int64_t N, int64_t K, int64_t ldx, in
 }
 
 // y = x @ w.T (+ bias) (then tanh-GELU); x [M, K], w [N, K] bf16; epi: 0 none, 1 bias, 5 bias + GELU
-torch::Tensor linear_decode(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, int64_t epi) {
+// tickets: the one-launch form (kernels.h), at least N / 16 int32 zeros on the device, left zero
+torch::Tensor linear_decode(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, int64_t epi,
+                            c10::optional<torch::Tensor> tickets) {
   TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16 &&
                   x.dim() == 2 && w.dim() == 2 && x.stride(1) == 1 && w.stride(1) == 1 && x.device() == w.device(),
               "linear_decode: x [M, K] and w [N, K] must be bf16 tensors on one ROCm device with unit column stride");
@@ -2156,12 +2172,13 @@ torch::Tensor linear_decode(torch::Tensor x, torch::Tensor w, c10::optional<torc
                 "linear_decode: bias must be a contiguous bf16 [N] device tensor");
     bp = bias->data_ptr();
   }
+  int* tk = decode_tickets("linear_decode", tickets, x, N / 16, "one per 16 output columns");
   auto y = torch::empty({M, N}, x.options());
   const size_t wsn = sdml::linear_decode_workspace_floats((int)M, (int)N, (int)K);
   torch::Tensor ws;
   if (wsn) ws = torch::empty({(int64_t)wsn}, x.options().dtype(torch::kFloat32));
   sdml::linear_decode_bf16(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), wsn ? ws.data_ptr<float>() : nullptr, (int)M,
-                           (int)N, (int)K, (int)ldx, (int)ldw, (int)epi, cur_stream());
+                           (int)N, (int)K, (int)ldx, (int)ldw, (int)epi, cur_stream(), tk);
   return y;
 }
 
@@ -2285,10 +2302,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "sdml gfx950 HIP kernels";
   m.def("attention_decode", &attention_decode,
         "one new token per sample against a KV cache (bf16, d=64): writes k, v at row lens[b], returns [B, C]",
-        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("n_keys"));
+        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("n_keys"),
+        py::arg("tickets") = py::none());
   m.def("attention_decode_chunk", []() { return sdml::kAttnDecodeChunk; }, "keys per wave of attention_decode");
   m.def("linear_decode", &linear_decode, "x @ w.T (+ bias) (GELU) for M <= 64 rows, weight-streaming (bf16)",
-        py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("epi") = 0);
+        py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("epi") = 0,
+        py::arg("tickets") = py::none());
   m.def("linear_decode_supported", &linear_decode_supported_op, "shapes linear_decode takes (M, N, K, ldx, ldw)");
   m.def("linear_decode_splits", [](int64_t N, int64_t K) { return sdml::linear_decode_splits((int)N, (int)K); },
         "grid-level K splits of linear_decode for (N, K)");

@@ -11,7 +11,8 @@ token data, ``--data_seed`` + 1 as in ``train``). ``--temperature 0`` (default) 
 --top_p P`` samples with noise keyed by (``--seed``, sample, position), see parallel/generate.py. ``--eos_token E``
 ends a row after it draws E (``--pad_token`` fills what follows, ``--stop_check N`` is how often the host looks
 whether all rows have ended). With ``--ragged`` or ``--eos_token`` a printed line holds the row's tokens up to its own
-length. ``--metrics`` gets one ``generate`` event: the tokens really generated, seconds, tokens/s.
+length. ``--graph`` replays one captured decode step per token (one rank on a ROCm device, bf16, head width 64; the
+same tokens). ``--metrics`` gets one ``generate`` event: the tokens really generated, seconds, tokens/s, graph.
 """
 from __future__ import annotations
 
@@ -68,6 +69,8 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--pad_token", type=int, default=0, help="fills a row after its end")
     s.add_argument("--stop_check", type=int, default=16,
                    help="with --eos_token: steps between the host's looks whether all rows ended (0: never)")
+    s.add_argument("--graph", action="store_true",
+                   help="replay one captured decode step per token (hipGraph; one rank, ROCm bf16, head width 64)")
     return p
 
 
@@ -114,6 +117,8 @@ def _prompts(args, spec):
 def run(args) -> dict:
     cli.export_env(args)
     device = _device(args)
+    if args.graph and device.type != "cuda":
+        raise SystemExit(f"--graph replays a captured step on a ROCm device; this run is on {device}")
     stages = args.stages or DEFAULT_STAGES[args.model]
     pp = args.pp or min(stages, max(1, args.world_size // max(1, args.tp)))
     pp = max(1, min(pp, args.world_size // max(1, args.tp)))
@@ -137,7 +142,7 @@ def run(args) -> dict:
         out, lengths = generate(engine, prompts, args.max_new_tokens, temperature=args.temperature,
                                 top_k=args.top_k, seed=args.seed, top_p=args.top_p, prompt_lens=plens,
                                 eos_token=args.eos_token, pad_token=args.pad_token, stop_check=args.stop_check,
-                                return_lengths=True)
+                                return_lengths=True, graph=args.graph)
         rows = out.cpu().tolist()  # (the read-back ends the timed region)
         lengths = lengths.cpu().tolist()
         dt_s = time.perf_counter() - t0
@@ -153,7 +158,7 @@ def run(args) -> dict:
             print(",".join(str(t) for t in r), flush=True)
         metrics.log(event="generate", samples=len(rows), prompt_len=prompts.shape[1], tokens=n_new, seconds=dt_s,
                     tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k,
-                    top_p=args.top_p)
+                    top_p=args.top_p, graph=bool(args.graph))
     return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
 
 

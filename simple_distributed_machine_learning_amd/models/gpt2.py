@@ -268,9 +268,11 @@ class GPT2Stage(PipelineStage):
         return lm_head(y, self.lm_head.weight) if last else x
 
     # ---- generation: KV cache, prefill, one decode step (ops/decode.py; parallel/generate.py drives them) ----------
-    def new_cache(self, B: int, Smax: int) -> "KVCache":
+    def new_cache(self, B: int, Smax: int, fused: bool = False) -> "KVCache":
         """An empty cache for B samples and up to Smax positions: K and V [B, Smax, H, D] per local layer, one
-        device-side length."""
+        device-side length. ``fused``: also the arrival counters of ``decode_step(fused=True)``, one zeroed int32
+        buffer with a slice of its own per call site (four projections and the attention of every local layer; the
+        lm_head is not split over K and needs none)."""
         if Smax > self.cfg.block_size:
             raise ValueError(f"a cache of {Smax} positions exceeds block_size={self.cfg.block_size}")
         if getattr(self, "tp", None) is not None:
@@ -279,8 +281,37 @@ class GPT2Stage(PipelineStage):
         H, D = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
         mk = lambda: torch.empty((B, Smax, H, D), dtype=p.dtype, device=p.device)  # noqa: E731
         n = len(self.h)
+        tickets = None
+        if fused:
+            tickets = torch.zeros(n * sum(self._ticket_sizes(B)), dtype=torch.int32, device=p.device)
         return KVCache([mk() for _ in range(n)], [mk() for _ in range(n)],
-                       torch.zeros(B, dtype=torch.int32, device=p.device), 0, Smax)
+                       torch.zeros(B, dtype=torch.int32, device=p.device), 0, Smax, tickets)
+
+    def _ticket_sizes(self, B: int):
+        """Counters per call site of one layer (DECODE_SITES order): a projection has one per 16 output columns, the
+        attention one per (sample, head). Each slice is padded to 16 bytes, so the buffer, zeroed as a whole from its
+        allocation's start, stays a multiple of 16 bytes."""
+        C = self.cfg.n_embd
+        inner = next(iter(self.h.values())).mlp.c_fc.weight.shape[0] if len(self.h) else 4 * C
+        raw = (3 * C // 16, B * self.cfg.n_head, C // 16, inner // 16, C // 16)
+        return tuple((v + 3) // 4 * 4 for v in raw)
+
+    def _ticket_views(self, cache: "KVCache"):
+        """Per local layer, {site: its slice of cache.tickets}; built once per cache."""
+        views = getattr(cache, "_views", None)
+        if views is None:
+            sizes = self._ticket_sizes(cache.lens.shape[0])
+            if cache.tickets is None or cache.tickets.numel() < len(self.h) * sum(sizes):
+                raise ValueError("decode_step(fused=True) needs a cache from new_cache(..., fused=True)")
+            views, o = [], 0
+            for _ in range(len(self.h)):
+                d = {}
+                for site, n in zip(DECODE_SITES, sizes):
+                    d[site] = cache.tickets[o:o + n]
+                    o += n
+                views.append(d)
+            cache._views = views
+        return views
 
     def _head_logits(self, y):
         """[B, ld] logits of rows y [B, C]: ld is the padded vocabulary where the weight sits in row-padded storage
@@ -339,12 +370,20 @@ class GPT2Stage(PipelineStage):
         return self._head_logits(y.reshape(B * S, C).index_select(0, rows))
 
     @torch.no_grad()
-    def decode_step(self, x, cache: "KVCache"):
+    def decode_step(self, x, cache: "KVCache", fused: bool = False):
         """One new token per sample. x: tokens [B] on stage 0, else [B, C]. Appends the token's k / v to the cache,
         advances the device-side length, returns [B, C] or on the last stage the logits [B, ld]. No host
-        synchronisation: positions come from ``cache.lens``."""
+        synchronisation: positions come from ``cache.lens``.
+
+        ``fused`` (a cache from ``new_cache(fused=True)``): the one-launch forms (ops/decode.py ``tickets``) at the
+        call sites of DECODE_FUSED_SITES, the four projections, and the attention over ``n_keys = smax`` so that no
+        launch depends on the step's index. The same bits as ``fused=False``, 8 launches per block for 12; this is
+        the step that parallel/decode_graph.py captures. The counters are zeroed once at the start of the
+        step, so a step that died midway cannot poison the next."""
         if cache.n + 1 > cache.smax:
             raise ValueError(f"the cache is full ({cache.n} of {cache.smax} positions)")
+        if fused:
+            return self._decode_step_fused(x, cache)
         if self.stage_id == 0:
             x = embedding_at(x, cache.lens, self.wte.weight, self.wpe.weight)
         last = self.stage_id == self.num_stages - 1
@@ -374,6 +413,52 @@ class GPT2Stage(PipelineStage):
             y = self.ln_f(x)
         return self._head_logits(y)
 
+    @torch.no_grad()
+    def _decode_step_fused(self, x, cache: "KVCache", _sites=None):
+        """decode_step's lines with the counters of the call sites in DECODE_FUSED_SITES passed in and the attention's
+        grid over the whole cache. ``_sites`` (tools/bench_generate.py only): other sites, to measure each one's
+        share."""
+        if cache.n + 1 > cache.smax:
+            raise ValueError(f"the cache is full ({cache.n} of {cache.smax} positions)")
+        sites = DECODE_FUSED_SITES if _sites is None else frozenset(_sites)
+        views = self._ticket_views(cache)
+        cache.tickets.zero_()
+        if self.stage_id == 0:
+            x = embedding_at(x, cache.lens, self.wte.weight, self.wpe.weight)
+        last = self.stage_id == self.num_stages - 1
+        blocks = list(self.h.values())
+        H = self.cfg.n_head
+        y = None
+        if blocks:
+            x, y = layer_norm_pass(x, blocks[0].ln_1)
+        for i, blk in enumerate(blocks):
+            at, mlp = blk.attn, blk.mlp
+            tk = {s: (v if s in sites else None) for s, v in views[i].items()}
+            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias, tickets=tk["c_attn"])
+            a = attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, cache.smax, tickets=tk["attn"])
+            a = linear_decode(a, at.c_proj.weight, at.c_proj.bias, tickets=tk["attn_proj"])
+            x, y = add_layer_norm(x, a, blk.ln_2)
+            m = linear_decode(y, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True, tickets=tk["c_fc"])
+            m = linear_decode(m, mlp.c_proj.weight, mlp.c_proj.bias, tickets=tk["mlp_proj"])
+            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
+            if nxt is None:
+                x = x + m
+            else:
+                x, y = add_layer_norm(x, m, nxt)
+        cache.lens.add_(1)
+        cache.n += 1
+        if not last:
+            return x
+        if y is None:
+            y = self.ln_f(x)
+        return self._head_logits(y)
+
+
+# the call sites of one block in decode_step, and those that run their one-launch form under fused=True (a site
+# measured slower inside the captured step stays on two launches: docs/TUNING_NOTES.md "Graph-replayed decode")
+DECODE_SITES = ("c_attn", "attn", "attn_proj", "c_fc", "mlp_proj")
+DECODE_FUSED_SITES = frozenset(DECODE_SITES) - {"attn"}  # (the attention: 2.7 % slower on one launch, kept on two)
+
 
 @dataclass
 class KVCache:
@@ -386,6 +471,7 @@ class KVCache:
     lens: torch.Tensor
     n: int
     smax: int
+    tickets: Optional[torch.Tensor] = None  # new_cache(fused=True): the arrival counters of decode_step(fused=True)
 
 
 def gpt2_spec(num_stages: int = 2, cfg: GPT2Config = None, seq_len: int = None, dtype=torch.bfloat16,

@@ -28,15 +28,22 @@ def linear_decode_supported(M: int, N: int, K: int, ldx: int = None, ldw: int = 
     return bool(kernels().linear_decode_supported(M, N, K, K if ldx is None else ldx, K if ldw is None else ldw))
 
 
-def linear_decode(x, w, b=None, gelu: bool = False):
+def linear_decode(x, w, b=None, gelu: bool = False, tickets=None):
     """y [M, N] = x [M, K] w[N, K]^T (+ b) (then tanh-GELU; needs b). ROCm bf16: linear_decode.hip for M <= 64 (W
-    streamed once over the whole chip), gemm_bf16.hip above that; anything else: torch."""
+    streamed once over the whole chip), gemm_bf16.hip above that; anything else: torch.
+
+    ``tickets``: the one-launch form of linear_decode.hip. An int32 tensor on x's device with at least N / 16 entries,
+    all zero on entry; the kernel leaves them zero. Where the shape is split over K, the last split to arrive at a
+    column tile sums the tile instead of a second launch; the bits are those of the call without tickets. A wrong
+    dtype, device or size is a RuntimeError. The torch twins and the M > 64 path ignore it."""
     if gelu and b is None:
         raise ValueError("linear_decode: the GELU epilogue comes with a bias")
     if _hip_bf16(x, w):
         epi = EPI_BIAS_GELU if gelu else (EPI_BIAS if b is not None else EPI_STORE)
         if x.shape[0] <= LINEAR_DECODE_MAX_M:
-            return kernels().linear_decode(x, w, b, epi)
+            if tickets is None:
+                return kernels().linear_decode(x, w, b, epi)
+            return kernels().linear_decode(x, w, b, epi, tickets)
         return kernels().gemm_bf16(x, w, b, False, epi)[0]
     y = F.linear(x, w, b)
     return F.gelu(y, approximate="tanh") if gelu else y
@@ -61,17 +68,27 @@ def attention_decode_ref(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int):
     return torch.einsum("bhs,bshd->bhd", p, vc).to(qkv.dtype).reshape(B, C)
 
 
-def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int):
+def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int, tickets=None):
     """One new token per sample against a KV cache. qkv [B, 3C]: the token's fused projection; k_cache / v_cache
     [B, Smax, H, D] (views with any row strides); lens int32 [B] on the device: keys already cached. Writes the new
     k, v to cache row lens[b] and returns the attention output [B, C] over keys 0..lens[b]. ``lens`` is not changed:
     the caller advances it once per step, on the device. ``n_keys`` is the host's bound lens[b] + 1 <= n_keys (the
-    caller counts the steps itself, so no length is read back); n_keys <= Smax or a ValueError."""
+    caller counts the steps itself, so no length is read back); n_keys <= Smax or a ValueError.
+
+    ``tickets``: the one-launch form of attention_decode.hip. An int32 tensor on qkv's device with at least B * H
+    entries, all zero on entry; the kernel leaves them zero. The last live chunk of a (sample, head) to arrive combines
+    the chunks instead of a second launch, so the caller may pass ``n_keys = Smax`` (the bound then never changes);
+    the bits are those of the call without tickets at any n_keys > max(lens). A wrong dtype, device or size is a
+    RuntimeError. The bound n_keys > max(lens) cannot be checked without reading the device: if it is violated, the
+    rows concerned are not written and their counters are left non-zero, so zero the tensor before using it again
+    (``decode_step`` passes Smax and zeroes its buffer every step). The torch twin ignores it."""
     Smax = k_cache.shape[1]
     if not 1 <= n_keys <= Smax:
         raise ValueError(f"attention_decode: {n_keys} keys with the new one, but the cache has {Smax} rows")
     D = k_cache.shape[-1]
     if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
+        if tickets is not None:
+            return kernels().attention_decode(qkv, k_cache, v_cache, lens, 1.0 / math.sqrt(D), int(n_keys), tickets)
         return kernels().attention_decode(qkv, k_cache, v_cache, lens, 1.0 / math.sqrt(D), int(n_keys))
     return attention_decode_ref(qkv, k_cache, v_cache, lens, n_head, n_keys)
 

@@ -20,9 +20,13 @@ nothing. The result is ``[B, Lmax + max_new_tokens]``: a row's prompt, its gener
 length, the pad token after. Only with an eos, every ``stop_check`` steps, the host reads one flag (are all rows done?),
 agreed through the pipeline group where there is one. A call without the three arguments runs the lines it always ran.
 
+``graph=True`` (one rank, ROCm bf16, head width 64) replays one captured decode step per token instead of issuing its
+launches from the host: parallel/decode_graph.py. The tokens and lengths are those of ``graph=False`` bit for bit.
+
 Limitations: tensor parallelism, data parallelism and ``--schedule rotate`` are refused. With pp ranks one rank works
 at a time (a token must leave the last stage before stage 0 can embed it); several sample groups in flight would fill
-the bubble and are not implemented.
+the bubble and are not implemented. ``graph=True`` is refused with pp > 1: the step's boundaries cross ranks between
+kernels, and a transport call cannot be part of a captured graph.
 """
 from __future__ import annotations
 
@@ -105,20 +109,31 @@ def _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_che
 @torch.no_grad()
 def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              seed: Optional[int] = None, sample0: int = 0, top_p: float = 1.0, prompt_lens=None,
-             eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False):
+             eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
+             graph: bool = False):
     """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
     ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
     samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
     ``pad_prompts``): ragged prompts, every row generating up to ``max_new_tokens`` tokens from its own length on.
     ``eos_token``: a row stops after drawing it; what follows is ``pad_token``. ``stop_check``: with an eos, the host
     asks every that many steps whether all rows are done (0: never; the result does not depend on it).
-    ``return_lengths``: (tokens, lengths int64 [B]), a row's prompt plus its generated tokens, the eos included."""
+    ``return_lengths``: (tokens, lengths int64 [B]), a row's prompt plus its generated tokens, the eos included.
+    ``graph``: replay one captured decode step per token (parallel/decode_graph.py; the same tokens and lengths). The
+    session stays on the engine, so the next call of the same shape and sampling arguments captures nothing."""
     from ..models.gpt2 import dropout_seed
 
     prompts, cfg = _check(engine, prompts, int(max_new_tokens))
     if temperature < 0:
         raise ValueError(f"generate: temperature must be >= 0, got {temperature}")
     lens_host = _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check)
+    if graph:
+        from .decode_graph import check_graph, generate_graphed
+
+        check_graph(engine, cfg)
+        if int(max_new_tokens) > 0:
+            return generate_graphed(engine, prompts, cfg, int(max_new_tokens), temperature, top_k,
+                                    dropout_seed(0 if seed is None else seed), sample0, top_p, lens_host, eos_token,
+                                    pad_token, stop_check, return_lengths)
     # the step kernel (sample + bookkeeping in one launch) serves the new arguments; without them: the lines below
     stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0
     mesh, dev, P = engine.mesh, engine.device, engine.P

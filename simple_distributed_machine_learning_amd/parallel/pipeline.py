@@ -220,6 +220,9 @@ class PipelineEngine:
         # buffers come from a persistent pool (no per-step communication allocations)
         self.transport = mesh.transport
         self.bufs = BufferPool(self.device)
+        # generate(..., graph=True): the one kept session (parallel/decode_graph.py) and how often a step was captured
+        self.decode_session = None
+        self.decode_graph_captures = 0
         self.grad_sync = GradSync(self.flat, mesh, self.local_stage_ids)
         if clip_grad:
             self._place_grad_norm(sched)

@@ -4,6 +4,7 @@ whole decode loop, hand-written against library-substituted, alternated in one p
     python tools/bench_generate.py [--B 16] [--ctx 512] [--rounds 3] [--sweep]
         [--out_kernels profiles/generate_kernels.jsonl] [--out_loop profiles/generate_gpt2.jsonl]
     python tools/bench_generate.py --ragged [--out_ragged profiles/ragged_generate.jsonl]
+    python tools/bench_generate.py --graph [--sweep] [--out_graph profiles/generate_graph.jsonl]
 
 Per kernel (one JSON line per kernel, shape and round): the time of one call, taken as a device-event window around
 --reps back-to-back calls, and the achieved GB/s of the bytes that must move: W for the projections (x and y are
@@ -27,6 +28,15 @@ hand kernels (the LayerNorm kernels are the same in both). The gate: hand >= lib
     reported only.
   * one decode-loop row: the loop with ragged cache lengths and sample_step doing the bookkeeping (token matrix, done
     flags, lengths, an eos set) against today's loop (sample_logits and the column store out[:, t] = tok).
+
+--graph measures the graph-replayed decode step (parallel/decode_graph.py) and writes --out_graph:
+  * per-kernel windows, one-launch (tickets) against two-launch, alternated over --rounds: the four projections at
+    M = B and attention_decode at ctx 128 / 512 / 1024;
+  * the decode loop in three forms, alternated over --rounds: (a) today's eager loop, (b) the captured step with the
+    two-launch kernels, (c) the captured step as decode_step(fused=True) runs it; then (c) with each call site
+    flipped (a one-launch site put back on two launches, a two-launch site put on one). The gate: (c) >= (a) in tokens/s in every round at --B 16 --ctx 512. --sweep adds the B x ctx grid.
+--graph --replays N only captures form (c) and replays it N times: the run to put under `rocprofv3 --kernel-trace
+--stats`, where a kernel's calls / (N + 1) are its launches per step (one eager step precedes the capture).
 """
 import argparse
 import json
@@ -41,9 +51,11 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from simple_distributed_machine_learning_amd import _native  # noqa: E402
 from simple_distributed_machine_learning_amd.models import get_model_spec  # noqa: E402
+from simple_distributed_machine_learning_amd.models.gpt2 import DECODE_FUSED_SITES, DECODE_SITES  # noqa: E402
 from simple_distributed_machine_learning_amd.ops.decode import sample_logits, sample_step  # noqa: E402
 from simple_distributed_machine_learning_amd.ops.transformer import add_layer_norm, layer_norm_pass  # noqa: E402
 from simple_distributed_machine_learning_amd.parallel import PipelineEngine, init_mesh  # noqa: E402
+from simple_distributed_machine_learning_amd.parallel.decode_graph import DecodeSession  # noqa: E402
 
 DEV = torch.device("cuda", 0)
 BF = torch.bfloat16
@@ -284,6 +296,144 @@ def bench_loop(engine, B, ctx, steps, rounds, emit, gate):
     return h >= l
 
 
+# ---- the graph-replayed step (--graph) -----------------------------------------------------------------------------
+def bench_fused_kernels(B, ctxs, rounds, reps, emit):
+    """One-launch (tickets) against two-launch windows of the decode kernels, operands as in bench_kernels."""
+    K = _native.kernels()
+    for name, (N, Kd) in SHAPES.items():
+        if name == "lm_head":  # not split over K: there is one launch either way
+            continue
+        copies = max(2, min(reps, LLC_BYTES // (N * Kd * 2) + 1))
+        w = torch.randn(copies, N, Kd, device=DEV, dtype=BF) * 0.02
+        b = torch.randn(N, device=DEV, dtype=BF)
+        x = torch.randn(B, Kd, device=DEV, dtype=BF)
+        tk = torch.zeros(N // 16, dtype=torch.int32, device=DEV)
+        epi = 5 if name == "c_fc" else 1
+        fns = {"two launches": lambda i: K.linear_decode(x, w[i % copies], b, epi),
+               "one launch": lambda i: K.linear_decode(x, w[i % copies], b, epi, tk)}
+        for fn in fns.values():
+            window(fn, copies)
+        for r in range(rounds):
+            for kname, fn in fns.items():  # alternated
+                ms = window(fn, reps)
+                emit({"kernel": "linear_decode", "form": kname, "shape": name, "M": B, "N": N, "K": Kd,
+                      "KS": K.linear_decode_splits(N, Kd), "round": r, "us": round(ms * 1e3, 2)})
+        del w
+    H, D = 12, 64
+    for ctx in ctxs:
+        Smax = ctx + 1
+        copies = max(2, min(reps, LLC_BYTES // (B * Smax * H * D * 2 * 2) + 1))
+        kc = torch.randn(copies, B, Smax, H, D, device=DEV, dtype=BF)
+        vc = torch.randn(copies, B, Smax, H, D, device=DEV, dtype=BF)
+        qkv = torch.randn(B, 3 * H * D, device=DEV, dtype=BF)
+        lens = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+        tk = torch.zeros(B * H, dtype=torch.int32, device=DEV)
+        fns = {"two launches": lambda i: K.attention_decode(qkv, kc[i % copies], vc[i % copies], lens, 0.125, Smax),
+               "one launch": lambda i: K.attention_decode(qkv, kc[i % copies], vc[i % copies], lens, 0.125, Smax, tk)}
+        for fn in fns.values():
+            window(fn, copies)
+        for r in range(rounds):
+            for kname, fn in fns.items():
+                ms = window(fn, reps)
+                emit({"kernel": "attention_decode", "form": kname, "B": B, "H": H, "ctx": ctx, "round": r,
+                      "us": round(ms * 1e3, 2)})
+        del kc, vc
+
+
+SAMPLE_KW = dict(vocab=50257, temperature=0.0, top_k=0, top_p=1.0, seed=0, sample0=0, eos=-1, pad=0)
+
+
+@torch.no_grad()
+def graph_session(engine, B, ctx, steps, sites):
+    """A captured step (generate(graph=True)'s session) over caches of ctx + steps rows with random contents."""
+    ctx = min(ctx, engine.stages[0].cfg.block_size - steps)
+    ses = DecodeSession(engine, None, B, ctx + steps, _sites=sites)
+    ses.capture(engine, SAMPLE_KW)
+    for c in ses.caches.values():
+        for t in c.k + c.v:
+            t.normal_()
+    return ses, ctx
+
+
+@torch.no_grad()
+def run_graph_loop(ses, ctx, steps):
+    """Seconds of `steps` replays from caches holding ctx keys."""
+    ses.reset()
+    for c in ses.caches.values():
+        c.lens.fill_(ctx)
+        c.n = ctx
+    ses.tok.random_(0, 50257)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        ses.replay()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def bench_graph_loop(engine, B, ctx, steps, rounds, emit, gate, sites):
+    forms = {"(a) eager": "eager", "(b) graph, two-launch kernels": (), "(c) graph, one-launch kernels": None}
+    if sites:
+        for s in DECODE_SITES:  # each site flipped against decode_step's choice
+            if s in DECODE_FUSED_SITES:
+                forms[f"(c) with {s} on two launches"] = tuple(DECODE_FUSED_SITES - {s})
+            else:
+                forms[f"(c) with {s} on one launch"] = tuple(DECODE_FUSED_SITES | {s})
+    ses = {k: graph_session(engine, B, ctx, steps, f) for k, f in forms.items() if f != "eager"}
+    run_loop(engine, B, ctx, 8, True)
+    for k, (se, c) in ses.items():
+        run_graph_loop(se, c, 8)
+    tps = {k: [] for k in forms}
+    for r in range(rounds):
+        for k in forms:  # alternated
+            s = run_loop(engine, B, ctx, steps, True) if forms[k] == "eager" else run_graph_loop(*ses[k], steps)
+            tps[k].append(B * steps / s)
+            emit({"loop": k, "B": B, "ctx": ctx, "steps": steps, "round": r, "ms_per_step": round(s / steps * 1e3, 4),
+                  "tokens_per_s": round(B * steps / s, 1)})
+    a, b, c = (tps[k] for k in list(forms)[:3])
+    rec = {"summary": "graph-replayed decode loop", "B": B, "ctx": ctx,
+           "eager_tokens_per_s": [round(v, 1) for v in a], "graph_two_launch_tokens_per_s": [round(v, 1) for v in b],
+           "graph_one_launch_tokens_per_s": [round(v, 1) for v in c],
+           "one_launch_over_eager": round(statistics.median(c) / statistics.median(a), 3),
+           "one_launch_over_two_launch": round(statistics.median(c) / statistics.median(b), 3)}
+    for k in list(forms)[3:]:
+        rec[k] = round(statistics.median(tps[k]) / statistics.median(c), 3)  # > 1: the flipped site is faster
+    ok = all(x >= y for x, y in zip(c, a))
+    if gate:
+        rec["gate_graph_at_least_eager_every_round"] = bool(ok)
+    emit(rec)
+    del ses
+    torch.cuda.empty_cache()
+    return ok
+
+
+def main_graph(a):
+    os.makedirs(os.path.dirname(a.out_graph) or ".", exist_ok=True)
+    mesh = init_mesh(pp=1, schedule_kind="1f1b", rank=0, world_size=1, device=DEV)
+    engine = PipelineEngine(get_model_spec("gpt2", 2), mesh, schedule_kind="1f1b", num_microbatches=1)
+    engine.eval()
+    if a.replays:
+        ses, ctx = graph_session(engine, a.B, a.ctx, a.replays, None)
+        s = run_graph_loop(ses, ctx, a.replays)
+        print(json.dumps({"replays": a.replays, "ms_per_step": round(s / a.replays * 1e3, 4)}), flush=True)
+        return 0
+    with open(a.out_graph, "w") as f:
+        def emit(rec):
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+
+        if not a.no_kernels:
+            bench_fused_kernels(a.B, sorted({128, a.ctx, 1024}), a.rounds, a.reps, emit)
+        ok = bench_graph_loop(engine, a.B, a.ctx, a.steps, a.rounds, emit, gate=True, sites=True)
+        if a.sweep:
+            for B in (1, 16, 64):
+                for ctx in (128, 1024):
+                    bench_graph_loop(engine, B, ctx, a.steps, a.rounds, emit, gate=False, sites=False)
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=16)
@@ -297,9 +447,14 @@ def main():
     ap.add_argument("--out_loop", default="profiles/generate_gpt2.jsonl")
     ap.add_argument("--ragged", action="store_true", help="only the step sampler's window and its decode-loop row")
     ap.add_argument("--out_ragged", default="profiles/ragged_generate.jsonl")
+    ap.add_argument("--graph", action="store_true", help="only the graph-replayed step: kernel windows and the loops")
+    ap.add_argument("--out_graph", default="profiles/generate_graph.jsonl")
+    ap.add_argument("--replays", type=int, default=0, help="with --graph: capture, replay this often, nothing else")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py measures on the GPU; none is visible")
+    if a.graph:
+        return main_graph(a)
     if a.ragged:
         os.makedirs(os.path.dirname(a.out_ragged) or ".", exist_ok=True)
         with open(a.out_ragged, "w") as f:
