@@ -519,6 +519,45 @@ struct AttnDecodeArgs {
 };
 int attention_decode_chunks(int n_keys);
 void attention_decode_bf16(const AttnDecodeArgs& a, hipStream_t stream);
+// T = 1 .. kAttnAppendMaxT new tokens per sample against the cache (attention_append.hip). qkv [B][T] rows of ldq
+// elements, nq [B] int32 on the device: live queries per sample. Query t is live iff t < nq[b] and lens[b] + t <
+// n_keys (the host's bound, 1 <= n_keys <= Smax; max_chunks = attention_decode_chunks(n_keys)). A live query writes
+// its k, v to cache row lens[b] + t and out [B][T][C] gets the bits attention_decode_bf16 gives that token with
+// lens[b] + t keys cached; a dead one writes no cache row and its out row is zeros. lens is not changed.
+// ws_ml: [B][T][H][max_chunks][2] fp32, ws_o: [B][T][H][max_chunks][64] fp32.
+constexpr int kAttnAppendMaxT = 8;
+struct AttnAppendArgs {
+  const void* qkv = nullptr;
+  void *k_cache = nullptr, *v_cache = nullptr, *out = nullptr;
+  const int *lens = nullptr, *nq = nullptr;
+  float *ws_ml = nullptr, *ws_o = nullptr;
+  int B = 0, T = 0, H = 0, Smax = 0, n_keys = 0, max_chunks = 0;
+  long ldq = 0, sb = 0, ss = 0, sh = 0;
+  float scale = 1.f;
+};
+void attention_append_bf16(const AttnAppendArgs& a, hipStream_t stream);
+// Prompt-lookup speculation: accept the verify step's drafts, then draft the next step's tokens from the row's own
+// history (lookup.hip; ops/reference.py lookup_step is the definition). g / tok_in [B][K + 1] int64 and nq_in [B]:
+// the sampler's tokens, the step's inputs (newest token, drafts) and 1 + the number of drafts; g == nullptr: nothing
+// to accept. out [B][ld_out] with W columns, lens / limit / done / gen_len / row_steps int32 [B]: the rows' state.
+// tok_next [B][K + 1], nq_next [B], all_done [1]: the next step's inputs.
+constexpr int kLookupMaxDrafts = 7;
+constexpr int kLookupMaxNgram = 8;
+struct LookupStepArgs {
+  const int64_t *g = nullptr, *tok_in = nullptr;
+  const int* nq_in = nullptr;
+  int64_t* out = nullptr;
+  long ld_out = 0;
+  int W = 0;
+  int* lens = nullptr;
+  const int* limit = nullptr;
+  int *done = nullptr, *gen_len = nullptr, *row_steps = nullptr;
+  int64_t* tok_next = nullptr;
+  int *nq_next = nullptr, *all_done = nullptr;
+  int B = 0, K = 0, N = 0;
+  int64_t eos = -1, pad = 0;
+};
+void lookup_step(const LookupStepArgs& a, hipStream_t stream);
 // y[M][N] = x[M][K] W[N][K]^T with epi EPI_STORE, EPI_BIAS or EPI_BIAS_GELU (bias [N] bf16); 1 <= M <=
 // kLinearDecodeMaxM, K % 64 == 0, N % 16 == 0, leading dimensions % 8 == 0, 16-B aligned operands, y contiguous.
 // ws: linear_decode_workspace_floats(M, N, K) fp32 (0: none). Deterministic; a row's bits do not depend on M.
@@ -533,9 +572,10 @@ void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y,
                         int ldx, int ldw, int epi, hipStream_t stream, int* tickets = nullptr);
 // out[r] (int64) = the token of row r of bf16 logits [rows][ld] among columns < vocab: inv_temp == 0 greedy, else
 // Gumbel-max at 1 / T = inv_temp over the top_k candidates (top_k <= 0 or >= vocab: all), noise keyed by
-// (seed, sample0 + r, pos[r], token) (sample.hip). pos: int32 [rows] on the device.
+// (seed, sample0 + r / rows_per_sample, pos[r], token) (sample.hip). pos: int32 [rows] on the device.
 void sample_logits_bf16(const void* logits, int rows, int ld, int vocab, float inv_temp, int top_k,
-                        unsigned long long seed, unsigned sample0, const int* pos, int64_t* out, hipStream_t stream);
+                        unsigned long long seed, unsigned sample0, const int* pos, int64_t* out, hipStream_t stream,
+                        int rows_per_sample = 1);
 // sample_logits' token with top-p and the generation step's bookkeeping in the same launch (sample.hip).
 // top_p outside (0, 1) or temperature == 0: no nucleus. tokens [rows] always gets the row's token. Optional (nullptr:
 // off): out [rows][ld_out] int64 with W columns gets the token at column pos[r]; gen_len [rows] grows by one; done
@@ -548,6 +588,7 @@ struct SampleStepArgs {
   double temperature = 0.0, top_p = 1.0;
   unsigned long long seed = 0;
   unsigned sample0 = 0;
+  int rows_per_sample = 1;  // row r belongs to sample sample0 + r / rows_per_sample
   const int* pos = nullptr;
   int64_t* tokens = nullptr;
   int64_t* out = nullptr;

@@ -14,6 +14,8 @@
 //       rkey = drop_row_key(drop_site_key(seed, 5 << 16), sample0 + row, 0);  word = drop_word(rkey, position, v)
 //     with the vocabulary id in the b4 slot (one word per candidate) and position = the index of the token being
 //     drawn. No step counter: a token is a function of (seed, sample, position, logits) alone.
+//   * rows_per_sample (default 1): row r is sample sample0 + r / rows_per_sample, so several positions of one sample
+//     may be drawn in one launch (the verify step of prompt-lookup speculation).
 //   NaN logits never win a comparison. Integer LDS atomics build the histograms; no float atomics anywhere.
 //
 // sample_step: sample_logits' token with two additions in the same launch (the device code above is shared).
@@ -69,6 +71,7 @@ struct SampleParams {
   float inv_temp;  // 0: greedy
   unsigned long long seed;
   unsigned sample0;
+  int rps;  // logits rows per sample (>= 1): row r belongs to sample sample0 + r / rps
 };
 
 // sample_step's additions: the nucleus and the step's bookkeeping (all optional: a null pointer switches a part off)
@@ -136,7 +139,7 @@ __device__ __forceinline__ int draw_token(const SampleParams& p, const u16* lg, 
   const bool greedy = p.inv_temp == 0.f;
   unsigned pk = 0;
   if (!greedy) {
-    const unsigned rkey = drop_row_key(drop_site_key(p.seed, (unsigned)DROP_SITE_SAMPLE << 16), p.sample0 + row, 0);
+    const unsigned rkey = drop_row_key(drop_site_key(p.seed, (unsigned)DROP_SITE_SAMPLE << 16), p.sample0 + (unsigned)(row / p.rps), 0);
     pk = rkey ^ ((unsigned)p.pos[row] * 0x9E3779B1u);  // drop_word(rkey, position, v) = fmix32(pk ^ v * 0x85EBCA77)
   }
   float best = 0.f;
@@ -321,7 +324,8 @@ __global__ void __launch_bounds__(256) embed_at_kernel(const int64_t* __restrict
 }  // namespace
 
 void sample_logits_bf16(const void* logits, int rows, int ld, int vocab, float inv_temp, int top_k,
-                        unsigned long long seed, unsigned sample0, const int* pos, int64_t* out, hipStream_t stream) {
+                        unsigned long long seed, unsigned sample0, const int* pos, int64_t* out, hipStream_t stream,
+                        int rows_per_sample) {
   if (rows <= 0) return;
   SampleParams p;
   p.logits = static_cast<const u16*>(logits);
@@ -331,6 +335,7 @@ void sample_logits_bf16(const void* logits, int rows, int ld, int vocab, float i
   p.inv_temp = inv_temp;
   p.seed = seed;
   p.sample0 = sample0;
+  p.rps = rows_per_sample > 0 ? rows_per_sample : 1;
   hipLaunchKernelGGL(sample_logits_kernel, dim3(rows), dim3(ST), 0, stream, p);
 }
 
@@ -344,6 +349,7 @@ void sample_step_bf16(const SampleStepArgs& a, hipStream_t stream) {
   q.s.inv_temp = a.temperature > 0.0 ? (float)(1.0 / a.temperature) : 0.f;
   q.s.seed = a.seed;
   q.s.sample0 = a.sample0;
+  q.s.rps = a.rows_per_sample > 0 ? a.rows_per_sample : 1;
   q.top_p = a.top_p;
   q.a_scale = a.temperature > 0.0 ? 1.4426950408889634 / a.temperature : 0.0;
   q.seq = a.out;

@@ -2145,6 +2145,104 @@ torch::Tensor attention_decode(torch::Tensor qkv, torch::Tensor k_cache, torch::
   return out;
 }
 
+// qkv [B, T, 3C] (T = 1..8 new tokens per sample), the caches as attention_decode takes them, lens / nq int32 [B] on
+// the device: keys already cached and live queries per sample. Query t is live iff t < nq[b] and lens[b] + t <
+// n_keys. Writes the live queries' k, v at cache rows lens[b] + t; returns [B, T, C], zeros for dead queries.
+torch::Tensor attention_append(torch::Tensor qkv, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor lens,
+                               torch::Tensor nq, double scale, int64_t n_keys) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 3 && qkv.stride(2) == 1,
+              "attention_append: qkv must be a [B, T, 3C] bf16 device tensor with unit column stride");
+  const int64_t B = qkv.size(0), T = qkv.size(1);
+  TORCH_CHECK(T >= 1 && T <= sdml::kAttnAppendMaxT, "attention_append: T = ", T, " new tokens per sample, 1..",
+              sdml::kAttnAppendMaxT, " are supported");
+  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.scalar_type() == torch::kBFloat16 &&
+                  v_cache.scalar_type() == torch::kBFloat16 && k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() &&
+                  k_cache.strides() == v_cache.strides(),
+              "attention_append: k_cache / v_cache must be bf16 device tensors [B, Smax, H, 64] of one layout");
+  const int64_t Smax = k_cache.size(1), H = k_cache.size(2), C = H * 64;
+  TORCH_CHECK(k_cache.size(3) == 64 && k_cache.stride(3) == 1, "attention_append: head width 64, contiguous channels");
+  TORCH_CHECK(k_cache.size(0) == B && qkv.size(2) == 3 * C, "attention_append: qkv ", qkv.sizes(), " does not match a ",
+              k_cache.sizes(), " cache");
+  TORCH_CHECK(k_cache.device() == qkv.device() && v_cache.device() == qkv.device() && lens.device() == qkv.device() &&
+                  nq.device() == qkv.device(),
+              "attention_append: all tensors on one device");
+  for (int d = 0; d < 3; ++d)
+    TORCH_CHECK(k_cache.stride(d) % 8 == 0 && k_cache.stride(d) >= 0, "attention_append: cache strides must be multiples of 8");
+  TORCH_CHECK(qkv.stride(1) % 8 == 0 && qkv.stride(1) >= 3 * C && (B == 1 || qkv.stride(0) == T * qkv.stride(1)) &&
+                  aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache),
+              "attention_append: qkv rows must be 16-byte aligned with one stride over [B, T]");
+  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() && lens.dim() == 1 && lens.numel() == B,
+              "attention_append: lens must be int32 [B] on the device");
+  TORCH_CHECK(nq.scalar_type() == torch::kInt32 && nq.is_contiguous() && nq.dim() == 1 && nq.numel() == B,
+              "attention_append: nq must be int32 [B] on the device");
+  TORCH_CHECK(n_keys >= 1 && n_keys <= Smax, "attention_append: n_keys = ", n_keys, " outside 1..", Smax,
+              " (the cache's rows)");
+  TORCH_CHECK(B >= 1 && B <= 65535 && H <= 65535, "attention_append: batch / heads out of the grid's range");
+  sdml::AttnAppendArgs a;
+  a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
+  auto out = torch::empty({B, T, C}, qkv.options());
+  auto ws = torch::empty({B * T * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
+  a.qkv = qkv.data_ptr(), a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr(), a.out = out.data_ptr();
+  a.lens = lens.data_ptr<int>(), a.nq = nq.data_ptr<int>();
+  a.ws_o = ws.data_ptr<float>();
+  a.ws_ml = a.ws_o + B * T * H * a.max_chunks * 64;
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Smax = (int)Smax, a.n_keys = (int)n_keys;
+  a.ldq = qkv.stride(1), a.sb = k_cache.stride(0), a.ss = k_cache.stride(1), a.sh = k_cache.stride(2);
+  a.scale = (float)scale;
+  sdml::attention_append_bf16(a, cur_stream());
+  return out;
+}
+
+// Prompt-lookup speculation's accept + draft (kernels.h LookupStepArgs; ops/reference.py lookup_step). g, tok_in
+// int64 [B, K + 1] and nq_in int32 [B], or all three None: nothing to accept. out int64 [B, W]; lens, limit, done,
+// gen_len, row_steps int32 [B]. Returns (tok_next int64 [B, K + 1], nq_next int32 [B], all_done int32 [1]).
+std::vector<torch::Tensor> lookup_step(c10::optional<torch::Tensor> g, c10::optional<torch::Tensor> tok_in,
+                                       c10::optional<torch::Tensor> nq_in, torch::Tensor out, torch::Tensor lens,
+                                       torch::Tensor limit, torch::Tensor done, torch::Tensor gen_len,
+                                       torch::Tensor row_steps, int64_t K, int64_t N, int64_t eos, int64_t pad) {
+  TORCH_CHECK(K >= 1 && K <= sdml::kLookupMaxDrafts, "lookup_step: K = ", K, " drafts, 1..", sdml::kLookupMaxDrafts,
+              " are supported");
+  TORCH_CHECK(N >= 1 && N <= sdml::kLookupMaxNgram, "lookup_step: n-gram length ", N, ", 1..", sdml::kLookupMaxNgram,
+              " are supported");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kInt64 && out.dim() == 2 && out.size(0) >= 1 &&
+                  out.size(1) >= 1 && out.size(1) <= INT_MAX && out.stride(1) == 1 &&
+                  (out.size(0) <= 1 || out.stride(0) >= out.size(1)),
+              "lookup_step: out must be an int64 [B, W] device tensor with unit column stride");
+  const int64_t B = out.size(0), T = K + 1;
+  for (const auto* t : {&lens, &limit, &done, &gen_len, &row_steps})
+    TORCH_CHECK(t->is_cuda() && t->device() == out.device() && t->scalar_type() == torch::kInt32 && t->is_contiguous() &&
+                    t->dim() == 1 && t->numel() == B,
+                "lookup_step: lens, limit, done, gen_len and row_steps must be contiguous int32 [B] device tensors");
+  TORCH_CHECK(eos >= -1 && pad >= 0, "lookup_step: eos / pad out of range");
+  const bool accept = g.has_value() && g->defined();
+  TORCH_CHECK(accept == (tok_in.has_value() && tok_in->defined()) && accept == (nq_in.has_value() && nq_in->defined()),
+              "lookup_step: g, tok_in and nq_in come together");
+  sdml::LookupStepArgs a;
+  if (accept) {
+    for (const auto* t : {&*g, &*tok_in})
+      TORCH_CHECK(t->is_cuda() && t->device() == out.device() && t->scalar_type() == torch::kInt64 &&
+                      t->is_contiguous() && t->numel() == B * T,
+                  "lookup_step: g and tok_in must be contiguous int64 [B, K + 1] device tensors");
+    TORCH_CHECK(nq_in->is_cuda() && nq_in->device() == out.device() && nq_in->scalar_type() == torch::kInt32 &&
+                    nq_in->is_contiguous() && nq_in->numel() == B,
+                "lookup_step: nq_in must be a contiguous int32 [B] device tensor");
+    a.g = g->data_ptr<int64_t>(), a.tok_in = tok_in->data_ptr<int64_t>(), a.nq_in = nq_in->data_ptr<int>();
+  }
+  auto tok_next = torch::empty({B, T}, out.options());
+  auto nq_next = torch::empty({B}, lens.options());
+  auto all_done = torch::empty({1}, lens.options());
+  a.out = out.data_ptr<int64_t>();
+  a.ld_out = B > 1 ? (long)out.stride(0) : (long)out.size(1);
+  a.W = (int)out.size(1);
+  a.lens = lens.data_ptr<int>(), a.limit = limit.data_ptr<int>(), a.done = done.data_ptr<int>();
+  a.gen_len = gen_len.data_ptr<int>(), a.row_steps = row_steps.data_ptr<int>();
+  a.tok_next = tok_next.data_ptr<int64_t>(), a.nq_next = nq_next.data_ptr<int>(), a.all_done = all_done.data_ptr<int>();
+  a.B = (int)B, a.K = (int)K, a.N = (int)N;
+  a.eos = eos, a.pad = pad;
+  sdml::lookup_step(a, cur_stream());
+  return {tok_next, nq_next, all_done};
+}
+
 bool linear_decode_supported_op(int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw) {
   if (M > INT_MAX || N > INT_MAX || K > INT_MAX || ldx > INT_MAX || ldw > INT_MAX) return false;
   return sdml::linear_decode_supported((int)M, (int)N, (int)K, (int)ldx, (int)ldw);
@@ -2184,7 +2282,8 @@ torch::Tensor linear_decode(torch::Tensor x, torch::Tensor w, c10::optional<torc
 
 // tokens [B] int64 from bf16 logits [B, ld] (columns < vocab); temperature 0: greedy. pos: int32 [B] on the device.
 torch::Tensor sample_logits(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, int64_t seed,
-                            int64_t sample0, torch::Tensor pos) {
+                            int64_t sample0, torch::Tensor pos, int64_t rows_per_sample) {
+  TORCH_CHECK(rows_per_sample >= 1 && rows_per_sample <= INT_MAX, "sample_logits: rows_per_sample must be >= 1");
   TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kBFloat16 && logits.dim() == 2 &&
                   logits.stride(1) == 1 && (logits.size(0) <= 1 || logits.stride(0) >= logits.size(1)),
               "sample_logits: logits must be a [B, ld] bf16 device tensor with unit column stride");
@@ -2201,7 +2300,8 @@ torch::Tensor sample_logits(torch::Tensor logits, int64_t vocab, double temperat
   TORCH_CHECK(temperature == 0.0 || (inv_temp > 0.f && std::isfinite(inv_temp)), "sample_logits: temperature out of range");
   const int k = (int)std::max<int64_t>(0, std::min<int64_t>(top_k, vocab));
   sdml::sample_logits_bf16(logits.data_ptr(), (int)B, (int)ld, (int)vocab, inv_temp, k, (unsigned long long)seed,
-                           (unsigned)sample0, pos.data_ptr<int>(), out.data_ptr<int64_t>(), cur_stream());
+                           (unsigned)sample0, pos.data_ptr<int>(), out.data_ptr<int64_t>(), cur_stream(),
+                           (int)rows_per_sample);
   return out;
 }
 
@@ -2238,8 +2338,10 @@ static sdml::SampleStepArgs sample_step_args(const char* who, const torch::Tenso
 torch::Tensor sample_step(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, double top_p,
                           int64_t seed, int64_t sample0, torch::Tensor pos, c10::optional<torch::Tensor> out,
                           c10::optional<torch::Tensor> done, c10::optional<torch::Tensor> gen_len, int64_t eos,
-                          int64_t pad) {
+                          int64_t pad, int64_t rows_per_sample) {
   auto a = sample_step_args("sample_step", logits, vocab, temperature, top_k, top_p, seed, sample0, pos);
+  TORCH_CHECK(rows_per_sample >= 1 && rows_per_sample <= INT_MAX, "sample_step: rows_per_sample must be >= 1");
+  a.rows_per_sample = (int)rows_per_sample;
   const int64_t B = logits.size(0);
   TORCH_CHECK(eos >= -1 && eos < vocab && pad >= 0 && pad < vocab, "sample_step: eos / pad outside the vocabulary");
   if (out) {
@@ -2304,6 +2406,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one new token per sample against a KV cache (bf16, d=64): writes k, v at row lens[b], returns [B, C]",
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("n_keys"),
         py::arg("tickets") = py::none());
+  m.def("attention_append", &attention_append,
+        "T = 1..8 new tokens per sample against a KV cache (bf16, d=64): writes the live queries' k, v at rows "
+        "lens[b] + t, returns [B, T, C] with attention_decode's bits per query",
+        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("nq"), py::arg("scale"),
+        py::arg("n_keys"));
+  m.def("lookup_step", &lookup_step,
+        "prompt-lookup speculation: accept the verify step's drafts, draft the next step's tokens (one launch)",
+        py::arg("g"), py::arg("tok_in"), py::arg("nq_in"), py::arg("out"), py::arg("lens"), py::arg("limit"),
+        py::arg("done"), py::arg("gen_len"), py::arg("row_steps"), py::arg("K"), py::arg("N"), py::arg("eos") = -1,
+        py::arg("pad") = 0);
   m.def("attention_decode_chunk", []() { return sdml::kAttnDecodeChunk; }, "keys per wave of attention_decode");
   m.def("linear_decode", &linear_decode, "x @ w.T (+ bias) (GELU) for M <= 64 rows, weight-streaming (bf16)",
         py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("epi") = 0,
@@ -2313,12 +2425,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grid-level K splits of linear_decode for (N, K)");
   m.def("sample_logits", &sample_logits, "greedy / top-k Gumbel-max sampling of bf16 logits rows on the device",
         py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("seed"),
-        py::arg("sample0"), py::arg("pos"));
+        py::arg("sample0"), py::arg("pos"), py::arg("rows_per_sample") = 1);
   m.def("sample_step", &sample_step,
         "sample_logits with top-p and the step's bookkeeping (token matrix, done flags, lengths) in one launch",
         py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
         py::arg("seed"), py::arg("sample0"), py::arg("pos"), py::arg("out") = py::none(),
-        py::arg("done") = py::none(), py::arg("gen_len") = py::none(), py::arg("eos") = -1, py::arg("pad") = 0);
+        py::arg("done") = py::none(), py::arg("gen_len") = py::none(), py::arg("eos") = -1, py::arg("pad") = 0,
+        py::arg("rows_per_sample") = 1);
   m.def("top_p_threshold", &top_p_threshold, "the candidate threshold of sample_step as a logit value, bf16 [B]",
         py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"));
   m.def("embedding_at", &embedding_at, "wte[tok[b]] + wpe[pos[b]] (bf16)");

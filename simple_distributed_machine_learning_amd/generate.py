@@ -12,7 +12,10 @@ token data, ``--data_seed`` + 1 as in ``train``). ``--temperature 0`` (default) 
 ends a row after it draws E (``--pad_token`` fills what follows, ``--stop_check N`` is how often the host looks
 whether all rows have ended). With ``--ragged`` or ``--eos_token`` a printed line holds the row's tokens up to its own
 length. ``--graph`` replays one captured decode step per token (one rank on a ROCm device, bf16, head width 64; the
-same tokens). ``--metrics`` gets one ``generate`` event: the tokens really generated, seconds, tokens/s, graph.
+same tokens). ``--lookup K --lookup_ngram N`` is prompt-lookup speculation (one rank): every step verifies K tokens
+drafted from the row's own history, matched on its last N tokens; the same tokens in fewer steps, and ``--stop_check``
+then counts verify steps. ``--metrics`` gets one ``generate`` event: the tokens really generated, seconds, tokens/s,
+graph, lookup, lookup_ngram, steps and tokens per step.
 """
 from __future__ import annotations
 
@@ -68,9 +71,15 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--eos_token", type=int, default=None, help="a row ends after it draws this token")
     s.add_argument("--pad_token", type=int, default=0, help="fills a row after its end")
     s.add_argument("--stop_check", type=int, default=16,
-                   help="with --eos_token: steps between the host's looks whether all rows ended (0: never)")
+                   help="with --eos_token or --lookup: steps between the host's looks whether all rows ended "
+                        "(0: never)")
     s.add_argument("--graph", action="store_true",
                    help="replay one captured decode step per token (hipGraph; one rank, ROCm bf16, head width 64)")
+    s.add_argument("--lookup", type=int, default=0, metavar="K",
+                   help="prompt-lookup speculation: verify K drafted tokens per row and step (0: off, at most 7; one "
+                        "rank, not with --graph)")
+    s.add_argument("--lookup_ngram", type=int, default=2, metavar="N",
+                   help="with --lookup: draft what followed the last earlier occurrence of the row's last N tokens (1..8)")
     return p
 
 
@@ -139,17 +148,20 @@ def run(args) -> dict:
     metrics = JsonlMetrics(args.metrics if mesh.is_master() else None, mesh.rank)
     try:
         t0 = time.perf_counter()
-        out, lengths = generate(engine, prompts, args.max_new_tokens, temperature=args.temperature,
-                                top_k=args.top_k, seed=args.seed, top_p=args.top_p, prompt_lens=plens,
-                                eos_token=args.eos_token, pad_token=args.pad_token, stop_check=args.stop_check,
-                                return_lengths=True, graph=args.graph)
+        res = generate(engine, prompts, args.max_new_tokens, temperature=args.temperature,
+                       top_k=args.top_k, seed=args.seed, top_p=args.top_p, prompt_lens=plens,
+                       eos_token=args.eos_token, pad_token=args.pad_token, stop_check=args.stop_check,
+                       return_lengths=True, graph=args.graph, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
+                       return_stats=not args.graph)
+        out, lengths = res[0], res[1]
+        steps = res[2]["steps"] if len(res) > 2 else None
         rows = out.cpu().tolist()  # (the read-back ends the timed region)
         lengths = lengths.cpu().tolist()
         dt_s = time.perf_counter() - t0
     except ValueError as e:  # the refusals (tp, dp, rotate, lengths): their message, not a traceback
         shutdown(mesh)
         raise SystemExit(str(e))
-    if plens is not None or args.eos_token is not None:  # each row up to its own length
+    if plens is not None or args.eos_token is not None or args.lookup:  # each row up to its own length
         rows = [r[:n] for r, n in zip(rows, lengths)]
     n_prompt = len(rows) * prompts.shape[1] if plens is None else int(plens.sum())
     n_new = sum(lengths) - n_prompt  # the tokens really generated (the eos included)
@@ -158,7 +170,8 @@ def run(args) -> dict:
             print(",".join(str(t) for t in r), flush=True)
         metrics.log(event="generate", samples=len(rows), prompt_len=prompts.shape[1], tokens=n_new, seconds=dt_s,
                     tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k,
-                    top_p=args.top_p, graph=bool(args.graph))
+                    top_p=args.top_p, graph=bool(args.graph), lookup=args.lookup, lookup_ngram=args.lookup_ngram,
+                    steps=steps, tokens_per_step=None if not steps else n_new / steps)
     return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
 
 

@@ -29,7 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .base import ModelSpec, PipelineStage
-from ..ops.decode import attention_decode, embedding_at, linear_decode
+from ..ops.decode import (ATTENTION_APPEND_MAX_T, LINEAR_DECODE_MAX_M, attention_append, attention_decode, embedding_at,
+                          linear_decode)
 from ..ops.linear import Linear, _w_padded, linear, lm_head, mlp_gelu
 from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
                              dropout_threshold)
@@ -409,6 +410,64 @@ class GPT2Stage(PipelineStage):
         cache.n += 1
         if not last:
             return x
+        if y is None:
+            y = self.ln_f(x)
+        return self._head_logits(y)
+
+    @torch.no_grad()
+    def decode_block(self, x, cache: "KVCache", nq):
+        """T = 1..8 new tokens per sample in one pass: the verify step of prompt-lookup speculation
+        (parallel/generate.py lookup=K). x: tokens [B, T] on stage 0, else [B, T, C]; ``nq`` int32 [B] on the device:
+        the sample's live tokens, 0..T. Token t of sample b sits at position lens[b] + t (clamped to block_size - 1
+        for a dead one) and a live one attends to the cache plus tokens 0..t of its sample, whose k / v go to cache
+        rows lens[b] + t. ``decode_step``'s kernels run over the B * T rows, with ``attention_append`` for the
+        attention; each of them computes a row from that row alone, so a live row's bits are those of the
+        ``decode_step`` that would have processed the token (docs/NUMERICS.md). Returns [B, T, C], or on the last
+        stage the logits [B * T, ld] of all rows (row b * T + t).
+
+        The device-side length is NOT advanced: the caller's ``lookup_step`` does that by the accepted count, so the
+        stages of one rank must share one ``cache.lens`` tensor. ``cache.n`` becomes the host's bound min(n + T,
+        smax). On ROCm bf16 B * T <= 64 is required (``linear_decode``'s rows): more rows would take another GEMM
+        with other bits, and are refused."""
+        if x.dim() < 2 or not 1 <= x.shape[1] <= ATTENTION_APPEND_MAX_T:
+            raise ValueError(f"decode_block: x must be [B, T(, C)] with T in 1..{ATTENTION_APPEND_MAX_T}, got "
+                             f"{tuple(x.shape)}")
+        B, T = x.shape[0], x.shape[1]
+        p = next(self.parameters())
+        if p.is_cuda and p.dtype == torch.bfloat16 and B * T > LINEAR_DECODE_MAX_M:
+            raise ValueError(f"decode_block: {B} samples x {T} tokens = {B * T} rows, but the decode projections take "
+                             f"at most {LINEAR_DECODE_MAX_M} rows per step")
+        if B != cache.lens.shape[0]:
+            raise ValueError(f"decode_block: {B} samples into a cache of {cache.lens.shape[0]}")
+        n_keys = min(cache.n + T, cache.smax)
+        if self.stage_id == 0:
+            pos = cache.lens[:, None] + torch.arange(T, dtype=torch.int32, device=cache.lens.device)[None, :]
+            pos = pos.clamp_(max=self.cfg.block_size - 1).reshape(B * T)
+            x = embedding_at(x.reshape(B * T), pos, self.wte.weight, self.wpe.weight)
+        else:
+            x = x.reshape(B * T, x.shape[-1])
+        last = self.stage_id == self.num_stages - 1
+        blocks = list(self.h.values())
+        H = self.cfg.n_head
+        y = None
+        if blocks:
+            x, y = layer_norm_pass(x, blocks[0].ln_1)
+        for i, blk in enumerate(blocks):
+            at, mlp = blk.attn, blk.mlp
+            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias)
+            a = attention_append(qkv.view(B, T, -1), cache.k[i], cache.v[i], cache.lens, nq, H, n_keys)
+            a = linear_decode(a.view(B * T, -1), at.c_proj.weight, at.c_proj.bias)
+            x, y = add_layer_norm(x, a, blk.ln_2)
+            m = linear_decode(linear_decode(y, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True), mlp.c_proj.weight,
+                              mlp.c_proj.bias)
+            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
+            if nxt is None:
+                x = x + m
+            else:
+                x, y = add_layer_norm(x, m, nxt)
+        cache.n = n_keys
+        if not last:
+            return x.view(B, T, -1)
         if y is None:
             y = self.ln_f(x)
         return self._head_logits(y)

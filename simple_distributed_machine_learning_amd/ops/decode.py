@@ -1,5 +1,5 @@
-"""Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, linear_decode.hip,
-sample.hip) and their torch twins.
+"""Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, attention_append.hip,
+linear_decode.hip, sample.hip, lookup.hip) and their torch twins.
 
 Dispatch: ROCm bf16 tensors (head width 64 for the attention) run the hand-written kernels, and a shape the kernels do
 not take is an error there, never a library call. CPU tensors, fp32 and other head widths run the twins below, which
@@ -17,6 +17,8 @@ from . import reference as _ref
 
 EPI_STORE, EPI_BIAS, EPI_BIAS_GELU = 0, 1, 5  # csrc/kernels/kernels.h GemmEpi
 LINEAR_DECODE_MAX_M = 64  # kLinearDecodeMaxM
+ATTENTION_APPEND_MAX_T = 8  # kAttnAppendMaxT
+LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM = 7, 8  # kLookupMaxDrafts, kLookupMaxNgram
 
 
 def _hip_bf16(*ts) -> bool:
@@ -93,6 +95,76 @@ def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int, tick
     return attention_decode_ref(qkv, k_cache, v_cache, lens, n_head, n_keys)
 
 
+def attention_append_ref(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
+    """The twin: query t of sample b is live iff t < nq[b] and lens[b] + t < n_keys. A live query writes its k, v at
+    cache row lens[b] + t and returns softmax(q_t K[0..lens[b]+t]^T / sqrt(D)) V[0..lens[b]+t] in fp32, which is
+    ``attention_decode_ref`` for that token with lens[b] + t keys cached; a dead query writes nothing and returns
+    zeros. Rows past a query's own are selected away (they may hold NaN patterns)."""
+    B, T, C3 = qkv.shape
+    C = C3 // 3
+    D = C // n_head
+    Smax = k_cache.shape[1]
+    rows = torch.arange(B, device=qkv.device)
+    keys = torch.arange(n_keys, device=qkv.device)[None, :]
+    out = torch.zeros((B, T, C), dtype=qkv.dtype, device=qkv.device)
+    for t in range(T):
+        q, k, v = (qkv[:, t, i * C:(i + 1) * C].view(B, n_head, D) for i in range(3))
+        at = lens.to(torch.int64) + t
+        alive = (nq.to(torch.int64) > t) & (at < n_keys)  # [B]
+        idx = at.clamp(0, Smax - 1)
+        sel = alive[:, None, None]
+        k_cache[rows, idx] = torch.where(sel, k, k_cache[rows, idx])
+        v_cache[rows, idx] = torch.where(sel, v, v_cache[rows, idx])
+        live = (keys <= idx[:, None]) & alive[:, None]  # [B, n_keys]
+        kc = torch.where(live[:, :, None, None], k_cache[:, :n_keys], torch.zeros_like(k_cache[:, :n_keys])).float()
+        vc = torch.where(live[:, :, None, None], v_cache[:, :n_keys], torch.zeros_like(v_cache[:, :n_keys])).float()
+        s = torch.einsum("bhd,bshd->bhs", q.float(), kc) * (1.0 / math.sqrt(D))
+        s = s.masked_fill(~live[:, None, :], -math.inf).masked_fill(~alive[:, None, None], 0.0)
+        o = torch.einsum("bhs,bshd->bhd", torch.softmax(s, dim=-1), vc).to(qkv.dtype).reshape(B, C)
+        out[:, t] = torch.where(alive[:, None], o, torch.zeros_like(o))
+    return out
+
+
+def attention_append(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
+    """T = 1..8 new tokens per sample against a KV cache (attention_append.hip). qkv [B, T, 3C]: the tokens' fused
+    projections; the caches and ``lens`` as ``attention_decode`` takes them; ``nq`` int32 [B] on the device: the
+    sample's live queries, 0..T. Query t is live iff t < nq[b] and lens[b] + t < n_keys (the host's bound on the rows
+    in use, 1 <= n_keys <= Smax or a ValueError): it writes its k, v to cache row lens[b] + t and its output row is,
+    bit for bit on the kernels, what ``attention_decode`` returns for that token with lens[b] + t keys cached. A dead
+    query writes no cache row and returns zeros. Returns [B, T, C]; ``lens`` is not changed."""
+    T = qkv.shape[1] if qkv.dim() == 3 else 0
+    if not 1 <= T <= ATTENTION_APPEND_MAX_T:
+        raise ValueError(f"attention_append: qkv must be [B, T, 3C] with T in 1..{ATTENTION_APPEND_MAX_T}, got "
+                         f"{tuple(qkv.shape)}")
+    Smax = k_cache.shape[1]
+    if not 1 <= n_keys <= Smax:
+        raise ValueError(f"attention_append: n_keys = {n_keys}, but the cache has {Smax} rows")
+    for name, t in (("lens", lens), ("nq", nq)):
+        if t.dtype != torch.int32 or t.shape != (qkv.shape[0],):
+            raise ValueError(f"attention_append: {name} must be int32 [B], got {t.dtype} {tuple(t.shape)}")
+    D = k_cache.shape[-1]
+    if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
+        return kernels().attention_append(qkv, k_cache, v_cache, lens, nq, 1.0 / math.sqrt(D), int(n_keys))
+    return attention_append_ref(qkv, k_cache, v_cache, lens, nq, n_head, n_keys)
+
+
+def lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, k: int, ngram: int, eos: int = -1,
+                pad: int = 0):
+    """Prompt-lookup speculation's bookkeeping, one launch per verify step: accept the step's drafts against the
+    sampler's tokens ``g``, then draft the next step's tokens from the row's own history (ops/reference.py lookup_step
+    is the definition). Returns (tok_next [B, k + 1], nq_next [B], all_done [1]). Device tensors: lookup.hip, integer
+    work with no host synchronisation; CPU tensors: the twin."""
+    if not 1 <= int(k) <= LOOKUP_MAX_DRAFTS:
+        raise ValueError(f"lookup_step: k must be in 1..{LOOKUP_MAX_DRAFTS}, got {k}")
+    if not 1 <= int(ngram) <= LOOKUP_MAX_NGRAM:
+        raise ValueError(f"lookup_step: ngram must be in 1..{LOOKUP_MAX_NGRAM}, got {ngram}")
+    if out.is_cuda:
+        return tuple(kernels().lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, int(k),
+                                           int(ngram), int(eos), int(pad)))
+    return _ref.lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, int(k), int(ngram), int(eos),
+                            int(pad))
+
+
 def embedding_at(tok, pos, wte, wpe):
     """wte[tok[b]] + wpe[pos[b]] -> [B, C] for tok int64 [B] and pos int32 [B] on the device."""
     if _hip_bf16(wte, wpe) and tok.is_cuda and wte.shape[1] % 4 == 0:
@@ -100,24 +172,32 @@ def embedding_at(tok, pos, wte, wpe):
     return F.embedding(tok, wte) + F.embedding(pos.to(torch.int64), wpe)
 
 
-def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int, sample0: int, positions):
+def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int, sample0: int, positions,
+                  rows_per_sample: int = 1):
     """Tokens int64 [B] from logits [B, ld]: greedy at temperature 0, else top-k Gumbel-max keyed by
-    (seed, sample0 + row, positions[row], token) (ops/reference.py sample_logits is the definition). ROCm bf16: the
-    on-device sampler, no host synchronisation."""
+    (seed, sample0 + row // rows_per_sample, positions[row], token) (ops/reference.py sample_logits is the
+    definition). ROCm bf16: the on-device sampler, no host synchronisation."""
+    if int(rows_per_sample) < 1:
+        raise ValueError(f"sample_logits: rows_per_sample must be >= 1, got {rows_per_sample}")
     if _hip_bf16(logits):
         return kernels().sample_logits(logits, int(vocab), float(temperature), int(top_k), int(seed), int(sample0),
-                                       positions)
-    return _ref.sample_logits(logits, vocab, temperature, top_k, seed, sample0, positions)
+                                       positions, int(rows_per_sample))
+    return _ref.sample_logits(logits, vocab, temperature, top_k, seed, sample0, positions, int(rows_per_sample))
 
 
 def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float, seed: int, sample0: int, positions,
-                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0):
+                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0, rows_per_sample: int = 1):
     """sample_logits over the top-p nucleus of the top-k candidates, with one generation step's bookkeeping in the
     same launch (ops/reference.py sample_step is the definition): tokens int64 [B]; ``out`` int64 [B, W] gets the token
     at column positions[row], ``gen_len`` int32 [B] grows by one, ``done`` int32 [B] is set on ``eos`` (-1: none); a
-    row already done emits ``pad`` and changes nothing. ROCm bf16: the on-device sampler, no host synchronisation."""
+    row already done emits ``pad`` and changes nothing. ``rows_per_sample``: row r is sample sample0 + r //
+    rows_per_sample (the verify step of prompt-lookup speculation draws several positions of a sample at once). ROCm
+    bf16: the on-device sampler, no host synchronisation."""
+    if int(rows_per_sample) < 1:
+        raise ValueError(f"sample_step: rows_per_sample must be >= 1, got {rows_per_sample}")
     if _hip_bf16(logits):
         return kernels().sample_step(logits, int(vocab), float(temperature), int(top_k), float(top_p), int(seed),
-                                     int(sample0), positions, out, done, gen_len, int(eos), int(pad))
+                                     int(sample0), positions, out, done, gen_len, int(eos), int(pad),
+                                     int(rows_per_sample))
     return _ref.sample_step(logits, vocab, temperature, top_k, top_p, seed, sample0, positions, out, done, gen_len,
-                            eos, pad)
+                            eos, pad, int(rows_per_sample))

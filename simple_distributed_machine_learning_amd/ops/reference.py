@@ -368,10 +368,12 @@ def _first_argmax(score, cand):
     return torch.where(tok == V, torch.zeros_like(tok), tok)
 
 
-def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int, sample0: int, positions):
+def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int, sample0: int, positions,
+                  rows_per_sample: int = 1):
     """Tokens [B] int64 from logits [B, ld] (columns < vocab take part). temperature == 0: greedy (argmax, lowest index
     on ties). temperature > 0: Gumbel-max over the top-k candidates, argmax_v(l_v * (1 / T) + g_v) in fp32 with one
-    multiply and one add, noise from sample_uniforms for samples sample0 + row and the given positions [B]."""
+    multiply and one add, noise from sample_uniforms for samples sample0 + row // rows_per_sample and the given
+    positions [B] (rows_per_sample > 1: several positions of one sample in one call)."""
     if temperature < 0:
         raise ValueError(f"temperature must be >= 0, got {temperature}")
     z = logits[:, :vocab]
@@ -380,14 +382,14 @@ def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int,
     if temperature == 0:
         return _first_argmax(zf, cand)
     B = z.shape[0]
-    samples = torch.arange(sample0, sample0 + B, dtype=torch.int64, device=z.device)
+    samples = sample0 + torch.arange(B, dtype=torch.int64, device=z.device) // int(rows_per_sample)
     g = gumbel_from_uniform(sample_uniforms(seed, samples, positions, vocab))
     inv_t = torch.tensor(1.0 / float(temperature), dtype=torch.float32, device=z.device)
     return _first_argmax(zf * inv_t + g, cand)
 
 
 def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float, seed: int, sample0: int, positions,
-                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0):
+                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0, rows_per_sample: int = 1):
     """sample_logits over the nucleus (top_p_candidates) plus one generation step's bookkeeping, in place. Returns the
     step's tokens [B]. Per row, with pos = positions[row]: a row whose ``done`` flag is set emits ``pad`` and changes
     nothing; else the token goes to out[row, pos], gen_len[row] grows by one and done[row] is set when the token is
@@ -404,7 +406,7 @@ def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float
     if temperature == 0:
         tok = _first_argmax(zf, cand)
     else:
-        samples = torch.arange(sample0, sample0 + B, dtype=torch.int64, device=z.device)
+        samples = sample0 + torch.arange(B, dtype=torch.int64, device=z.device) // int(rows_per_sample)
         g = gumbel_from_uniform(sample_uniforms(seed, samples, positions, vocab))
         inv_t = torch.tensor(1.0 / float(temperature), dtype=torch.float32, device=z.device)
         tok = _first_argmax(zf * inv_t + g, cand)
@@ -421,3 +423,78 @@ def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float
     if done is not None:
         done |= (write & (tok == eos)).to(done.dtype)
     return tok
+
+
+# ---- generation: prompt-lookup speculation (csrc/kernels/lookup.hip) ---------------------------------------------
+def lookup_drafts(hist, ngram: int, k: int, limit: int):
+    """(start, drafts) for a row's history ``hist`` (int64 [L + 1]: the tokens up to the newest, at column L): start
+    = the largest s <= L - ngram with hist[s : s + ngram] == hist[L - ngram + 1 : L + 1] (-1: none, or fewer than
+    ngram + 1 tokens), drafts = hist[s + ngram + i] for i < n = min(k, L - s - ngram + 1, limit - 2 - L): what followed
+    the most recent earlier occurrence of the last ``ngram`` tokens, as far as the row's width ``limit`` has room for
+    the drafts and the token after them."""
+    L = hist.shape[0] - 1
+    if L < ngram:
+        return -1, hist[:0]
+    win = hist.unfold(0, ngram, 1)[:L - ngram + 1]  # starts 0 .. L - ngram
+    hits = (win == hist[L - ngram + 1:]).all(1).nonzero()
+    if hits.numel() == 0:
+        return -1, hist[:0]
+    s = int(hits[-1])
+    n = max(0, min(k, L - s - ngram + 1, limit - 2 - L))
+    return s, hist[s + ngram:s + ngram + n]
+
+
+def lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, k: int, ngram: int, eos: int = -1,
+                pad: int = 0):
+    """One bookkeeping launch of prompt-lookup speculation, in place; the definition of csrc/kernels/lookup.hip.
+
+    State per row b: ``out`` int64 [B, W] the token matrix; ``lens[b]`` the cache length, which is also the column of
+    the row's newest token (not yet in the cache); ``limit[b]`` the row's final width (clamped to W); ``done``,
+    ``gen_len``, ``row_steps`` int32 [B]. A row is full when lens[b] + 1 >= limit[b]; a done or full row changes
+    nothing.
+
+    Accept (``g`` int64 [B, k + 1] given, with the step's inputs ``tok_in`` [B, k + 1] = newest token + drafts and
+    ``nq_in`` [B] = 1 + the number of drafts): a = the number of leading drafts d[i] = tok_in[b, 1 + i] with d[i] ==
+    g[b, i]; the row emits g[b, 0..a], cut so that column lens[b] + 1 + i < limit[b] and after the first ``eos``
+    (kept). The tokens go to out[b, lens[b] + 1 + i], gen_len[b] and lens[b] grow by the count, done[b] is set on an
+    eos, row_steps[b] grows by one. ``g`` None: nothing to accept (the first drafts, after the eagerly sampled token).
+
+    Draft (with the new lens): ``lookup_drafts`` of out[b, 0 .. lens[b]].
+
+    Returns (tok_next int64 [B, k + 1]: the newest token, the drafts, ``pad`` in the unused slots; nq_next int32 [B]:
+    1 + the number of drafts; all_done int32 [1]: 1 iff every nq_next is 0). A done or full row has nq_next 0 and
+    ``pad`` throughout."""
+    B, W = out.shape
+    T = k + 1
+    tok_next = torch.full((B, T), int(pad), dtype=torch.int64, device=out.device)
+    nq_next = torch.zeros(B, dtype=torch.int32, device=out.device)
+    for b in range(B):
+        L = int(lens[b])
+        lim = min(int(limit[b]), W)
+        dn = bool(done[b]) or L < 0 or L >= W
+        if g is not None and not dn and L + 1 < lim:
+            n = max(0, min(int(nq_in[b]) - 1, k))
+            a = 0
+            while a < n and int(tok_in[b, 1 + a]) == int(g[b, a]):
+                a += 1
+            cnt = min(a + 1, lim - 1 - L)
+            for i in range(cnt):
+                if int(g[b, i]) == eos:
+                    cnt, dn = i + 1, True
+                    break
+            out[b, L + 1:L + 1 + cnt] = g[b, :cnt]
+            L += cnt
+            lens[b] = L
+            gen_len[b] += cnt
+            row_steps[b] += 1
+            if dn:
+                done[b] = 1
+        if dn or L + 1 >= lim:
+            continue
+        _, drafts = lookup_drafts(out[b, :L + 1], ngram, k, lim)
+        n = drafts.shape[0]
+        tok_next[b, 0] = out[b, L]
+        tok_next[b, 1:1 + n] = drafts
+        nq_next[b] = 1 + n
+    all_done = (nq_next.max() == 0).to(torch.int32).reshape(1)
+    return tok_next, nq_next, all_done

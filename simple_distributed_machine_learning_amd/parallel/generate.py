@@ -23,10 +23,23 @@ agreed through the pipeline group where there is one. A call without the three a
 ``graph=True`` (one rank, ROCm bf16, head width 64) replays one captured decode step per token instead of issuing its
 launches from the host: parallel/decode_graph.py. The tokens and lengths are those of ``graph=False`` bit for bit.
 
+``lookup=K`` (1..7, one rank) is prompt-lookup speculation: after the prefill and the first token, every step verifies
+K drafted tokens per row next to the row's newest one. The drafts are what followed the most recent earlier occurrence
+of the row's last ``lookup_ngram`` tokens in its own history (``lookup_step``, on the device); ``decode_block`` runs
+the K + 1 positions in one pass and the sampler draws the token of every position, keyed by (seed, sample, position)
+as always; a row keeps the tokens up to and including the first one that differs from its draft. An accepted draft IS
+the token the plain loop would have drawn, so tokens and lengths are those of ``lookup=0``, bit for bit on the
+kernels (docs/NUMERICS.md), in fewer steps. Every sampling mode runs through the step bookkeeping here, so the result
+has the step sampler's layout. Every ``stop_check`` steps the host reads one flag (are all rows done or full?), with or
+without an eos: that is what ends the loop early. ``return_stats=True`` appends ``{"steps", "row_steps",
+"generated"}``.
+
 Limitations: tensor parallelism, data parallelism and ``--schedule rotate`` are refused. With pp ranks one rank works
 at a time (a token must leave the last stage before stage 0 can embed it); several sample groups in flight would fill
 the bubble and are not implemented. ``graph=True`` is refused with pp > 1: the step's boundaries cross ranks between
-kernels, and a transport call cannot be part of a captured graph.
+kernels, and a transport call cannot be part of a captured graph. ``lookup > 0`` is refused with ``graph=True`` (the
+verify step is not captured yet) and with pp > 1 (the other ranks' caches would need the accepted counts); on the
+kernels B * (K + 1) may not exceed 64 rows.
 """
 from __future__ import annotations
 
@@ -34,7 +47,7 @@ from typing import Optional
 
 import torch
 
-from ..ops.decode import sample_logits, sample_step
+from ..ops.decode import LINEAR_DECODE_MAX_M, LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, lookup_step, sample_logits, sample_step
 
 # message tags no schedule produces: message_tag() keeps mb * 4096 + stage in the bits above 2, and a schedule's
 # stage index is far below 4095
@@ -106,11 +119,32 @@ def _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_che
     return lens
 
 
+def _check_lookup(engine, cfg, B: int, lookup, lookup_ngram, graph: bool):
+    """The refusals of ``lookup`` / ``lookup_ngram``."""
+    if isinstance(lookup, bool) or not isinstance(lookup, int) or not 0 <= lookup <= LOOKUP_MAX_DRAFTS:
+        raise ValueError(f"generate: lookup must be an integer in 0..{LOOKUP_MAX_DRAFTS} (drafts per step), got "
+                         f"{lookup!r}")
+    if isinstance(lookup_ngram, bool) or not isinstance(lookup_ngram, int) or \
+            not 1 <= lookup_ngram <= LOOKUP_MAX_NGRAM:
+        raise ValueError(f"generate: lookup_ngram must be an integer in 1..{LOOKUP_MAX_NGRAM}, got {lookup_ngram!r}")
+    if lookup == 0:
+        return
+    if graph:
+        raise ValueError("generate: lookup > 0 with graph=True is not supported (the verify step is not captured yet)")
+    if engine.mesh.pp > 1:
+        raise ValueError(f"generate: lookup > 0 with pp={engine.mesh.pp} is not supported (the other ranks' caches "
+                         "would need the accepted counts); run one rank")
+    on_kernels = engine.device.type == "cuda" and engine.dtype == torch.bfloat16 and cfg.n_embd // cfg.n_head == 64
+    if on_kernels and B * (lookup + 1) > LINEAR_DECODE_MAX_M:
+        raise ValueError(f"generate: {B} samples x (lookup + 1 = {lookup + 1}) tokens = {B * (lookup + 1)} rows per "
+                         f"verify step, but the decode projections take at most {LINEAR_DECODE_MAX_M}")
+
+
 @torch.no_grad()
 def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              seed: Optional[int] = None, sample0: int = 0, top_p: float = 1.0, prompt_lens=None,
              eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
-             graph: bool = False):
+             graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False):
     """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
     ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
     samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
@@ -119,13 +153,21 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     asks every that many steps whether all rows are done (0: never; the result does not depend on it).
     ``return_lengths``: (tokens, lengths int64 [B]), a row's prompt plus its generated tokens, the eos included.
     ``graph``: replay one captured decode step per token (parallel/decode_graph.py; the same tokens and lengths). The
-    session stays on the engine, so the next call of the same shape and sampling arguments captures nothing."""
+    session stays on the engine, so the next call of the same shape and sampling arguments captures nothing.
+    ``lookup`` = K in 1..7: prompt-lookup speculation with K drafts per row and step, matched on the row's last
+    ``lookup_ngram`` tokens (module docstring); the same tokens and lengths in fewer steps. ``stop_check`` then counts
+    verify steps and is honoured without an eos too. ``return_stats``: a dict is appended to the result, ``steps`` (the
+    host's loop count), ``row_steps`` and ``generated`` (int64 [B] on the device: the steps in which the row emitted a
+    token, and its generated tokens)."""
     from ..models.gpt2 import dropout_seed
 
     prompts, cfg = _check(engine, prompts, int(max_new_tokens))
     if temperature < 0:
         raise ValueError(f"generate: temperature must be >= 0, got {temperature}")
     lens_host = _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check)
+    _check_lookup(engine, cfg, prompts.shape[0], lookup, lookup_ngram, graph)
+    if return_stats and graph:
+        raise ValueError("generate: return_stats is not available with graph=True")
     if graph:
         from .decode_graph import check_graph, generate_graphed
 
@@ -135,7 +177,7 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
                                     dropout_seed(0 if seed is None else seed), sample0, top_p, lens_host, eos_token,
                                     pad_token, stop_check, return_lengths)
     # the step kernel (sample + bookkeeping in one launch) serves the new arguments; without them: the lines below
-    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0
+    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0 or lookup > 0
     mesh, dev, P = engine.mesh, engine.device, engine.P
     sched = engine.schedule(1, True)
     owner = [sched.stage_rank(0, s) for s in range(P)]  # pipeline rank of each stage
@@ -160,13 +202,20 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     buf[:, total] = lens0 if stepped else total
     if new == 0:
         res = out.contiguous()
-        return (res, buf[:, total].clone()) if return_lengths else res
+        res = (res, buf[:, total].clone()) if return_lengths else res
+        if return_stats:
+            zeros = torch.zeros(B, dtype=torch.int64, device=dev)
+            res = (res if isinstance(res, tuple) else (res,)) + ({"steps": 0, "row_steps": zeros, "generated": zeros},)
+        return res
     nseed = dropout_seed(0 if seed is None else seed)
     mine = [s for s in range(P) if owner[s] == me and s in engine.stages]
     was_training = {s: engine.stages[s].training for s in mine}
     for s in mine:
         engine.stages[s].eval()
     caches = {s: engine.stages[s].new_cache(B, total) for s in mine}
+    if lookup:  # decode_block leaves the lengths to lookup_step: this rank's stages read one tensor
+        for s in mine[1:]:
+            caches[s].lens = caches[mine[0]].lens
     dt = engine.dtype
     C = cfg.n_embd
     first, last = owner[0], owner[P - 1]
@@ -230,9 +279,42 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
         tr.all_reduce(flag, channel="fwd", async_op=False)
         return bool(flag.item())
 
+    def lookup_loop() -> int:
+        """lookup > 0 (one rank): the prefill and the first token as always, then verify steps of K + 1 positions per
+        row. Returns the number of verify steps run."""
+        K, T = int(lookup), int(lookup) + 1
+        cache = caches[P - 1]
+        logits = run_stages(prompts, 0, prefill=True)
+        sample_step(logits, cfg.vocab_size, temperature, top_k, top_p, nseed, sample0, cache.lens, out, done, gen_len,
+                    eos, int(pad_token))
+        # from here on lens[b] is the column of row b's newest token, which is not in the cache yet
+        limit = (lens0 + new).to(torch.int32)
+        nxt, nq, flag = lookup_step(None, None, None, out, cache.lens, limit, done, gen_len, row_steps, K,
+                                    int(lookup_ngram), eos, int(pad_token))
+        offs = torch.arange(1, T + 1, dtype=torch.int32, device=dev)[None, :]
+        every = int(stop_check)
+        steps = 0
+        for it in range(new - 1):
+            x = nxt
+            for s in range(P):
+                x = engine.stages[s].decode_block(x, caches[s], nq)
+            pos = (cache.lens[:, None] + offs).reshape(B * T)  # the token drawn at row (b, t) sits at lens[b] + t + 1
+            g = sample_step(x, cfg.vocab_size, temperature, top_k, top_p, nseed, sample0, pos, rows_per_sample=T)
+            nxt, nq, flag = lookup_step(g.view(B, T), nxt, nq, out, cache.lens, limit, done, gen_len, row_steps, K,
+                                        int(lookup_ngram), eos, int(pad_token))
+            steps += 1
+            if every and steps % every == 0 and it + 1 < new - 1 and bool(flag.item()):
+                break
+        return steps
+
+    row_steps = torch.zeros(B, dtype=torch.int32, device=dev)
+    steps_run = 0
     try:
         tok = None
-        for t in range(new):  # token index S0 + t (ragged: lens[b] + t)
+        if lookup:
+            steps_run = lookup_loop()
+        # the plain loop (skipped after a lookup run): token index S0 + t (ragged: lens[b] + t)
+        for t in range(0 if lookup else new):
             x = (prompts if t == 0 else tok) if me == first else None
             logits = run_stages(x, t, prefill=(t == 0))
             if me == last:
@@ -247,6 +329,8 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
                 break
             if t + 1 < new:
                 tok = exchange_token(tok, t)
+        if not lookup:
+            steps_run = t + 1
         if stepped and me == last:
             buf[:, total] = lens0 + gen_len
         if tr is not None:
@@ -258,4 +342,10 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
         for s in mine:
             engine.stages[s].train(was_training[s])
     res = out.contiguous()
-    return (res, buf[:, total].clone()) if return_lengths else res
+    res = (res, buf[:, total].clone()) if return_lengths else res
+    if return_stats:
+        generated = buf[:, total] - lens0 if stepped else torch.full((B,), new, dtype=torch.int64, device=dev)
+        stats = {"steps": steps_run, "row_steps": row_steps.to(torch.int64) if lookup else generated.clone(),
+                 "generated": generated}
+        res = (res if isinstance(res, tuple) else (res,)) + (stats,)
+    return res
