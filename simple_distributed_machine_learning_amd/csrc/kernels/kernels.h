@@ -536,6 +536,20 @@ struct AttnAppendArgs {
   float scale = 1.f;
 };
 void attention_append_bf16(const AttnAppendArgs& a, hipStream_t stream);
+// Any T >= 1 new positions per sample against the cache plus themselves (attention_extend.hip): attention_append's
+// semantics (live iff t < nq[b] and lens[b] + t < n_keys; a live position writes its k, v to cache row lens[b] + t, a
+// dead one writes nothing and its out row is zeros; lens is not changed) on the training forward's arithmetic: with
+// cache rows [0, lens[b]) holding a full sequence's k, v, out row (b, t) of [B][T][C] has the bits of attention_fwd
+// (causal, 64-key tiles, one query sub-block) at position lens[b] + t. No workspace.
+struct AttnExtendArgs {
+  const void* qkv = nullptr;
+  void *k_cache = nullptr, *v_cache = nullptr, *out = nullptr;
+  const int *lens = nullptr, *nq = nullptr;
+  int B = 0, T = 0, H = 0, Smax = 0, n_keys = 0;
+  long ldq = 0, sb = 0, ss = 0, sh = 0;
+  float scale = 1.f;
+};
+void attention_extend_bf16(const AttnExtendArgs& a, hipStream_t stream);
 // Prompt-lookup speculation: accept the verify step's drafts, then draft the next step's tokens from the row's own
 // history (lookup.hip; ops/reference.py lookup_step is the definition). g / tok_in [B][K + 1] int64 and nq_in [B]:
 // the sampler's tokens, the step's inputs (newest token, drafts) and 1 + the number of drafts; g == nullptr: nothing

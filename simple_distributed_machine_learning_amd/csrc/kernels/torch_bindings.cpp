@@ -2193,6 +2193,51 @@ torch::Tensor attention_append(torch::Tensor qkv, torch::Tensor k_cache, torch::
   return out;
 }
 
+// qkv [B, T, 3C] (any T >= 1 new positions per sample, right-padded), the caches, lens and nq as attention_append takes
+// them. Position t is live iff t < nq[b] and lens[b] + t < n_keys. Writes the live positions' k, v at cache rows
+// lens[b] + t; returns [B, T, C] with attention_fwd's bits per position (attention_extend.hip), zeros for dead ones.
+torch::Tensor attention_extend(torch::Tensor qkv, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor lens,
+                               torch::Tensor nq, double scale, int64_t n_keys) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 3 && qkv.stride(2) == 1,
+              "attention_extend: qkv must be a [B, T, 3C] bf16 device tensor with unit column stride");
+  const int64_t B = qkv.size(0), T = qkv.size(1);
+  TORCH_CHECK(T >= 1, "attention_extend: T = ", T, " new positions per sample, at least 1");
+  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.scalar_type() == torch::kBFloat16 &&
+                  v_cache.scalar_type() == torch::kBFloat16 && k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() &&
+                  k_cache.strides() == v_cache.strides(),
+              "attention_extend: k_cache / v_cache must be bf16 device tensors [B, Smax, H, 64] of one layout");
+  const int64_t Smax = k_cache.size(1), H = k_cache.size(2), C = H * 64;
+  TORCH_CHECK(k_cache.size(3) == 64 && k_cache.stride(3) == 1, "attention_extend: head width 64, contiguous channels");
+  TORCH_CHECK(k_cache.size(0) == B && qkv.size(2) == 3 * C, "attention_extend: qkv ", qkv.sizes(), " does not match a ",
+              k_cache.sizes(), " cache");
+  TORCH_CHECK(k_cache.device() == qkv.device() && v_cache.device() == qkv.device() && lens.device() == qkv.device() &&
+                  nq.device() == qkv.device(),
+              "attention_extend: all tensors on one device");
+  for (int d = 0; d < 3; ++d)
+    TORCH_CHECK(k_cache.stride(d) % 8 == 0 && k_cache.stride(d) >= 0, "attention_extend: cache strides must be multiples of 8");
+  TORCH_CHECK(qkv.stride(1) % 8 == 0 && qkv.stride(1) >= 3 * C && (B == 1 || qkv.stride(0) == T * qkv.stride(1)) &&
+                  aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache),
+              "attention_extend: qkv rows must be 16-byte aligned with one stride over [B, T]");
+  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() && lens.dim() == 1 && lens.numel() == B,
+              "attention_extend: lens must be int32 [B] on the device");
+  TORCH_CHECK(nq.scalar_type() == torch::kInt32 && nq.is_contiguous() && nq.dim() == 1 && nq.numel() == B,
+              "attention_extend: nq must be int32 [B] on the device");
+  TORCH_CHECK(n_keys >= 1 && n_keys <= Smax, "attention_extend: n_keys = ", n_keys, " outside 1..", Smax,
+              " (the cache's rows)");
+  const int64_t nqb = (T + 127) / 128;
+  TORCH_CHECK(B >= 1 && B <= 65535 && H >= 1 && nqb * H * B < (1LL << 31) && B * T < (1LL << 31),
+              "attention_extend: batch / heads / positions out of the grid's range");
+  sdml::AttnExtendArgs a;
+  auto out = torch::empty({B, T, C}, qkv.options());
+  a.qkv = qkv.data_ptr(), a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr(), a.out = out.data_ptr();
+  a.lens = lens.data_ptr<int>(), a.nq = nq.data_ptr<int>();
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Smax = (int)Smax, a.n_keys = (int)n_keys;
+  a.ldq = qkv.stride(1), a.sb = k_cache.stride(0), a.ss = k_cache.stride(1), a.sh = k_cache.stride(2);
+  a.scale = (float)scale;
+  sdml::attention_extend_bf16(a, cur_stream());
+  return out;
+}
+
 // Prompt-lookup speculation's accept + draft (kernels.h LookupStepArgs; ops/reference.py lookup_step). g, tok_in
 // int64 [B, K + 1] and nq_in int32 [B], or all three None: nothing to accept. out int64 [B, W]; lens, limit, done,
 // gen_len, row_steps int32 [B]. Returns (tok_next int64 [B, K + 1], nq_next int32 [B], all_done int32 [1]).
@@ -2409,6 +2454,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_append", &attention_append,
         "T = 1..8 new tokens per sample against a KV cache (bf16, d=64): writes the live queries' k, v at rows "
         "lens[b] + t, returns [B, T, C] with attention_decode's bits per query",
+        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("nq"), py::arg("scale"),
+        py::arg("n_keys"));
+  m.def("attention_extend", &attention_extend,
+        "any T >= 1 new positions per sample against a KV cache plus themselves (bf16, d=64): writes the live "
+        "positions' k, v at rows lens[b] + t, returns [B, T, C] with attention_fwd's bits per position",
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("nq"), py::arg("scale"),
         py::arg("n_keys"));
   m.def("lookup_step", &lookup_step,

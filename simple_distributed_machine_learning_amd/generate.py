@@ -80,6 +80,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "rank, not with --graph)")
     s.add_argument("--lookup_ngram", type=int, default=2, metavar="N",
                    help="with --lookup: draft what followed the last earlier occurrence of the row's last N tokens (1..8)")
+    s.add_argument("--prefill_chunk", type=int, default=0, metavar="N",
+                   help="prefill the prompt in chunks of N positions through the extend-attention path (0: one pass; "
+                        "one rank, not with --graph or --lookup)")
     return p
 
 
@@ -152,7 +155,7 @@ def run(args) -> dict:
                        top_k=args.top_k, seed=args.seed, top_p=args.top_p, prompt_lens=plens,
                        eos_token=args.eos_token, pad_token=args.pad_token, stop_check=args.stop_check,
                        return_lengths=True, graph=args.graph, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
-                       return_stats=not args.graph)
+                       return_stats=not args.graph, prefill_chunk=args.prefill_chunk)
         out, lengths = res[0], res[1]
         steps = res[2]["steps"] if len(res) > 2 else None
         rows = out.cpu().tolist()  # (the read-back ends the timed region)

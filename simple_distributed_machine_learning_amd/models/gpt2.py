@@ -29,8 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .base import ModelSpec, PipelineStage
-from ..ops.decode import (ATTENTION_APPEND_MAX_T, LINEAR_DECODE_MAX_M, attention_append, attention_decode, embedding_at,
-                          linear_decode)
+from ..ops.decode import (ATTENTION_APPEND_MAX_T, LINEAR_DECODE_MAX_M, attention_append, attention_decode,
+                          attention_extend, embedding_at, linear_decode)
 from ..ops.linear import Linear, _w_padded, linear, lm_head, mlp_gelu
 from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
                              dropout_threshold)
@@ -369,6 +369,59 @@ class GPT2Stage(PipelineStage):
             return self._head_logits(y[:, -1].contiguous())
         rows = torch.arange(B, device=y.device) * S + (cache.lens.to(torch.int64) - 1)
         return self._head_logits(y.reshape(B * S, C).index_select(0, rows))
+
+    @torch.no_grad()
+    def extend(self, x, cache: "KVCache", nq=None):
+        """T new positions per sample into a cache that may already hold some: chunked prefill and the catch-up of a
+        generation session (parallel/session.py). x: tokens [B, T] on stage 0, else [B, T, C], right-padded, any T
+        with cache.n + T <= cache.smax; ``nq`` int32 [B] on the device: the sample's live positions, 0..T (None: all
+        T). Position t of sample b is lens[b] + t (clamped to block_size - 1 for the ``wpe`` lookup of a dead one).
+
+        The layer lines are ``prefill``'s, the modules' own GEMM calls, so a prompt position runs through the same
+        entry points whichever chunk carries it; ``attention_extend`` stands where ``prefill`` has
+        ``causal_attention`` plus the two cache copies. Afterwards ``cache.lens += nq`` and ``cache.n`` =
+        min(n + T, smax). Returns [B, T, C], or on the last stage the logits [B, ld] of each sample's last live
+        position (row nq[b] - 1, gathered on the device before the lm_head); the row of a sample with nq[b] == 0
+        holds unspecified values."""
+        if x.dim() < 2 or x.shape[1] < 1:
+            raise ValueError(f"extend: x must be [B, T(, C)] with T >= 1, got {tuple(x.shape)}")
+        B, T = x.shape[0], x.shape[1]
+        if B != cache.lens.shape[0] or cache.n + T > cache.smax:
+            raise ValueError(f"extend of {B} x {T} positions into a cache of {cache.lens.shape[0]} x {cache.smax} "
+                             f"holding {cache.n}")
+        dev = cache.lens.device
+        if nq is None:
+            nq = torch.full((B,), T, dtype=torch.int32, device=dev)
+        n_keys = cache.n + T
+        if self.stage_id == 0:
+            pos = cache.lens[:, None] + torch.arange(T, dtype=torch.int32, device=dev)[None, :]
+            pos = pos.clamp_(max=self.cfg.block_size - 1).reshape(B * T)
+            x = embedding_at(x.reshape(B * T), pos, self.wte.weight, self.wpe.weight).view(B, T, -1)
+        C = x.shape[-1]
+        last = self.stage_id == self.num_stages - 1
+        blocks = list(self.h.values())
+        H = self.cfg.n_head
+        y = None
+        if blocks:
+            x, y = layer_norm_pass(x, blocks[0].ln_1)
+        for i, blk in enumerate(blocks):
+            qkv = blk.attn.c_attn(y)
+            a = blk.attn.c_proj(attention_extend(qkv, cache.k[i], cache.v[i], cache.lens, nq, H, n_keys))
+            x, y = add_layer_norm(x, a, blk.ln_2)
+            m = blk.mlp(y)
+            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
+            if nxt is None:
+                x = x + m
+            else:
+                x, y = add_layer_norm(x, m, nxt)
+        cache.lens.add_(nq)
+        cache.n = n_keys
+        if not last:
+            return x
+        if y is None:
+            y = self.ln_f(x)
+        rows = torch.arange(B, device=dev) * T + (nq.to(torch.int64) - 1).clamp_(min=0)
+        return self._head_logits(y.reshape(B * T, C).index_select(0, rows))
 
     @torch.no_grad()
     def decode_step(self, x, cache: "KVCache", fused: bool = False):

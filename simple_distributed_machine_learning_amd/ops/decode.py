@@ -1,5 +1,5 @@
 """Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, attention_append.hip,
-linear_decode.hip, sample.hip, lookup.hip) and their torch twins.
+attention_extend.hip, linear_decode.hip, sample.hip, lookup.hip) and their torch twins.
 
 Dispatch: ROCm bf16 tensors (head width 64 for the attention) run the hand-written kernels, and a shape the kernels do
 not take is an error there, never a library call. CPU tensors, fp32 and other head widths run the twins below, which
@@ -146,6 +146,63 @@ def attention_append(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
     if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
         return kernels().attention_append(qkv, k_cache, v_cache, lens, nq, 1.0 / math.sqrt(D), int(n_keys))
     return attention_append_ref(qkv, k_cache, v_cache, lens, nq, n_head, n_keys)
+
+
+def attention_extend_ref(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
+    """The twin of ``attention_extend``: ``attention_append_ref``'s semantics at any T, one masked softmax per sample
+    in fp32 over keys 0..n_keys-1. The live positions' k, v go to cache rows lens[b] + t first; position t then sees
+    keys 0..lens[b]+t. Rows it does not see are selected away (they may hold NaN patterns); a dead position writes
+    nothing and returns zeros."""
+    B, T, C3 = qkv.shape
+    C = C3 // 3
+    D = C // n_head
+    Smax = k_cache.shape[1]
+    q, k, v = (qkv[..., i * C:(i + 1) * C].view(B, T, n_head, D) for i in range(3))
+    at = lens.to(torch.int64)[:, None] + torch.arange(T, device=qkv.device)[None, :]  # [B, T]: absolute positions
+    alive = (torch.arange(T, device=qkv.device)[None, :] < nq.to(torch.int64)[:, None]) & (at < n_keys) & \
+        (lens.to(torch.int64)[:, None] >= 0)
+    idx = at.clamp(0, Smax - 1)
+    rows = torch.arange(B, device=qkv.device)[:, None].expand(B, T)
+    sel = alive[:, :, None, None]
+    k_cache[rows[alive], idx[alive]] = k[alive]
+    v_cache[rows[alive], idx[alive]] = v[alive]
+    keys = torch.arange(n_keys, device=qkv.device)
+    live = (keys[None, None, :] <= idx[:, :, None]) & alive[:, :, None]  # [B, T, n_keys]
+    used = live.any(dim=1)[:, :, None, None]  # [B, n_keys, 1, 1]: rows some position of the sample sees
+    kc = torch.where(used, k_cache[:, :n_keys], torch.zeros_like(k_cache[:, :n_keys])).float()
+    vc = torch.where(used, v_cache[:, :n_keys], torch.zeros_like(v_cache[:, :n_keys])).float()
+    s = torch.einsum("bthd,bshd->bhts", q.float(), kc) * (1.0 / math.sqrt(D))
+    s = s.masked_fill(~live[:, None], -math.inf).masked_fill(~alive[:, None, :, None], 0.0)
+    o = torch.einsum("bhts,bshd->bthd", torch.softmax(s, dim=-1), vc).to(qkv.dtype)
+    return torch.where(sel, o, torch.zeros_like(o)).reshape(B, T, C)
+
+
+def attention_extend(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
+    """Any T >= 1 new positions per sample against a KV cache plus themselves (attention_extend.hip): chunked prefill
+    and a session's catch-up. qkv [B, T, 3C]: the chunk's fused projections, right-padded; the caches, ``lens`` and
+    ``nq`` as ``attention_append`` takes them. Position t is live iff t < nq[b] and lens[b] + t < n_keys (the host's
+    bound on the rows in use, 1 <= n_keys <= Smax or a ValueError): it writes its k, v to cache row lens[b] + t and
+    returns the causal attention over keys 0..lens[b]+t, on the kernels with the bits ``causal_attention`` gives that
+    position of the full sequence (docs/NUMERICS.md). A dead position writes no cache row and returns zeros. Returns
+    [B, T, C]; ``lens`` is not changed."""
+    if qkv.dim() != 3 or qkv.shape[1] < 1 or k_cache.dim() != 4 or k_cache.shape != v_cache.shape or \
+            qkv.shape[0] != k_cache.shape[0] or qkv.shape[2] != 3 * k_cache.shape[2] * k_cache.shape[3] or \
+            k_cache.shape[2] != n_head:
+        raise ValueError(f"attention_extend: qkv must be [B, T >= 1, 3C] against caches [B, Smax, H, D] with C = H D, "
+                         f"got {tuple(qkv.shape)}, {tuple(k_cache.shape)}, {tuple(v_cache.shape)}, n_head={n_head}")
+    if not (qkv.dtype == k_cache.dtype == v_cache.dtype):
+        raise ValueError(f"attention_extend: qkv and the caches must share one dtype, got {qkv.dtype}, "
+                         f"{k_cache.dtype}, {v_cache.dtype}")
+    Smax = k_cache.shape[1]
+    if not 1 <= n_keys <= Smax:
+        raise ValueError(f"attention_extend: n_keys = {n_keys}, but the cache has {Smax} rows")
+    for name, t in (("lens", lens), ("nq", nq)):
+        if t.dtype != torch.int32 or t.shape != (qkv.shape[0],):
+            raise ValueError(f"attention_extend: {name} must be int32 [B], got {t.dtype} {tuple(t.shape)}")
+    D = k_cache.shape[-1]
+    if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
+        return kernels().attention_extend(qkv, k_cache, v_cache, lens, nq, 1.0 / math.sqrt(D), int(n_keys))
+    return attention_extend_ref(qkv, k_cache, v_cache, lens, nq, n_head, n_keys)
 
 
 def lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, k: int, ngram: int, eos: int = -1,

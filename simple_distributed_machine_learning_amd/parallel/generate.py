@@ -34,6 +34,11 @@ has the step sampler's layout. Every ``stop_check`` steps the host reads one fla
 without an eos: that is what ends the loop early. ``return_stats=True`` appends ``{"steps", "row_steps",
 "generated"}``.
 
+``prefill_chunk=P`` (one rank) prefills the prompt through ``extend`` in chunks of P positions (models/gpt2.py; the
+extend-attention kernel) and then decodes as always; it runs on a ``GenerationSession`` (parallel/session.py), which is
+also how a cache outlives a call: more tokens, the next turn, appended tokens. It is refused with ``graph=True`` and
+with ``lookup > 0``.
+
 Limitations: tensor parallelism, data parallelism and ``--schedule rotate`` are refused. With pp ranks one rank works
 at a time (a token must leave the last stage before stage 0 can embed it); several sample groups in flight would fill
 the bubble and are not implemented. ``graph=True`` is refused with pp > 1: the step's boundaries cross ranks between
@@ -140,11 +145,32 @@ def _check_lookup(engine, cfg, B: int, lookup, lookup_ngram, graph: bool):
                          f"verify step, but the decode projections take at most {LINEAR_DECODE_MAX_M}")
 
 
+def _generate_chunked(engine, prompts, new, temperature, top_k, seed, sample0, top_p, lens_host, eos_token, pad_token,
+                      stop_check, return_lengths, return_stats, prefill_chunk):
+    """generate() with ``prefill_chunk`` > 0: a session of this call's length, its result in generate()'s form."""
+    from .session import GenerationSession
+
+    B, S0 = prompts.shape
+    s = GenerationSession(engine, prompts, S0 + new, prompt_lens=lens_host, pad_token=pad_token, seed=seed,
+                          sample0=sample0)
+    lens0 = s.lengths.to(torch.int64)
+    res, lengths = s.generate(new, temperature, top_k, top_p, eos_token, stop_check, prefill_chunk)
+    steps = s.steps
+    s.close()
+    res = (res, lengths) if return_lengths else res
+    if return_stats:
+        generated = lengths - lens0
+        res = (res if isinstance(res, tuple) else (res,)) + ({"steps": steps, "row_steps": generated.clone(),
+                                                              "generated": generated},)
+    return res
+
+
 @torch.no_grad()
 def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              seed: Optional[int] = None, sample0: int = 0, top_p: float = 1.0, prompt_lens=None,
              eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
-             graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False):
+             graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False,
+             prefill_chunk: int = 0):
     """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
     ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
     samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
@@ -158,7 +184,9 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     ``lookup_ngram`` tokens (module docstring); the same tokens and lengths in fewer steps. ``stop_check`` then counts
     verify steps and is honoured without an eos too. ``return_stats``: a dict is appended to the result, ``steps`` (the
     host's loop count), ``row_steps`` and ``generated`` (int64 [B] on the device: the steps in which the row emitted a
-    token, and its generated tokens)."""
+    token, and its generated tokens). ``prefill_chunk`` = P > 0 (one rank, not with ``graph`` or ``lookup``): the prompt
+    goes through ``extend`` in chunks of P positions instead of one ``prefill`` pass, on a ``GenerationSession``
+    (parallel/session.py) that lives for this call; 0 runs the lines it always ran."""
     from ..models.gpt2 import dropout_seed
 
     prompts, cfg = _check(engine, prompts, int(max_new_tokens))
@@ -166,8 +194,17 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
         raise ValueError(f"generate: temperature must be >= 0, got {temperature}")
     lens_host = _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check)
     _check_lookup(engine, cfg, prompts.shape[0], lookup, lookup_ngram, graph)
+    if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 0:
+        raise ValueError(f"generate: prefill_chunk must be an integer >= 0, got {prefill_chunk!r}")
+    if prefill_chunk > 0 and (graph or lookup > 0):
+        raise ValueError("generate: prefill_chunk > 0 with graph=True or lookup > 0 is not supported (the chunked "
+                         "prefill runs on a session, which neither path drives yet)")
     if return_stats and graph:
         raise ValueError("generate: return_stats is not available with graph=True")
+    if prefill_chunk > 0:
+        return _generate_chunked(engine, prompts, int(max_new_tokens), temperature, top_k, seed, sample0, top_p,
+                                 lens_host, eos_token, pad_token, stop_check, return_lengths, return_stats,
+                                 prefill_chunk)
     if graph:
         from .decode_graph import check_graph, generate_graphed
 
