@@ -550,6 +550,25 @@ struct AttnExtendArgs {
   float scale = 1.f;
 };
 void attention_extend_bf16(const AttnExtendArgs& a, hipStream_t stream);
+// One new token for each of R = G n rows, row g n + j being sibling j of group g (attention_fork.hip): the group's
+// plens[g] prompt keys sit once in k_prefix / v_prefix [G][Pmax][H][64] (strides psb, pss, psh; only read), the row's
+// later keys in k_suffix / v_suffix [R][Nmax][H][64] (strides ssb, sss, ssh), lens[r] = plens[g] + the row's suffix
+// keys. Writes the new k, v to suffix row lens[r] - plens[g] and out [R][C] gets the bits attention_decode_bf16 gives
+// that token on a cache holding the prompt rows followed by the suffix rows. A prompt chunk is loaded once for the n
+// siblings. The host guarantees lens[r] + 1 <= n_keys <= Pmax + Nmax, max_chunks = attention_decode_chunks(n_keys)
+// and 1 <= n <= kAttnForkMaxN; a row whose lengths fall outside the caches or n_keys is not indexed and not written.
+// ws_ml: [R][H][max_chunks][2] fp32, ws_o: [R][H][max_chunks][64] fp32.
+constexpr int kAttnForkMaxN = 64;
+struct AttnForkArgs {
+  const void *qkv = nullptr, *k_prefix = nullptr, *v_prefix = nullptr;
+  void *k_suffix = nullptr, *v_suffix = nullptr, *out = nullptr;
+  const int *plens = nullptr, *lens = nullptr;
+  float *ws_ml = nullptr, *ws_o = nullptr;
+  int G = 0, n = 0, H = 0, Pmax = 0, Nmax = 0, n_keys = 0, max_chunks = 0;
+  long ldq = 0, psb = 0, pss = 0, psh = 0, ssb = 0, sss = 0, ssh = 0;
+  float scale = 1.f;
+};
+void attention_fork_bf16(const AttnForkArgs& a, hipStream_t stream);
 // Prompt-lookup speculation: accept the verify step's drafts, then draft the next step's tokens from the row's own
 // history (lookup.hip; ops/reference.py lookup_step is the definition). g / tok_in [B][K + 1] int64 and nq_in [B]:
 // the sampler's tokens, the step's inputs (newest token, drafts) and 1 + the number of drafts; g == nullptr: nothing

@@ -2238,6 +2238,65 @@ torch::Tensor attention_extend(torch::Tensor qkv, torch::Tensor k_cache, torch::
   return out;
 }
 
+// qkv [R, 3C] (one new token for each of R = G n rows, row g n + j sibling j of group g), the prefix caches kp / vp
+// [G, Pmax, H, 64] with plens int32 [G] (the groups' prompt keys; only read), the suffix caches ks / vs [R, Nmax, H,
+// 64], lens int32 [R] = plens[g] + the row's suffix keys. n_keys: the host's bound lens[r] + 1 <= n_keys <= Pmax +
+// Nmax. Writes the new k, v at suffix row lens[r] - plens[g]; returns [R, C] with attention_decode's bits per row
+// (attention_fork.hip).
+torch::Tensor attention_fork(torch::Tensor qkv, torch::Tensor kp, torch::Tensor vp, torch::Tensor plens,
+                             torch::Tensor ks, torch::Tensor vs, torch::Tensor lens, int64_t n, double scale,
+                             int64_t n_keys) {
+  TORCH_CHECK(n >= 1 && n <= sdml::kAttnForkMaxN, "attention_fork: n = ", n, " samples per group, 1..",
+              sdml::kAttnForkMaxN, " are supported");
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1,
+              "attention_fork: qkv must be a [R, 3C] bf16 device tensor with unit column stride");
+  const int64_t R = qkv.size(0);
+  for (const auto* pr : {&kp, &ks}) {
+    const torch::Tensor &k = *pr, &v = pr == &kp ? vp : vs;
+    TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.scalar_type() == torch::kBFloat16 &&
+                    v.scalar_type() == torch::kBFloat16 && k.dim() == 4 && k.sizes() == v.sizes() &&
+                    k.strides() == v.strides(),
+                "attention_fork: kp / vp and ks / vs must be bf16 device tensors [rows, keys, H, 64], each pair of one "
+                "layout");
+    TORCH_CHECK(k.size(3) == 64 && k.stride(3) == 1, "attention_fork: head width 64, contiguous channels");
+    for (int d = 0; d < 3; ++d)
+      TORCH_CHECK(k.stride(d) % 8 == 0 && k.stride(d) >= 0, "attention_fork: cache strides must be multiples of 8");
+    TORCH_CHECK(k.device() == qkv.device() && v.device() == qkv.device(), "attention_fork: all tensors on one device");
+    TORCH_CHECK(aligned16(k) && aligned16(v), "attention_fork: 16-byte aligned rows required");
+  }
+  const int64_t G = kp.size(0), Pmax = kp.size(1), H = kp.size(2), Nmax = ks.size(1), C = H * 64;
+  TORCH_CHECK(G >= 1 && R == G * n && ks.size(0) == R && ks.size(2) == H && qkv.size(1) == 3 * C, "attention_fork: qkv ",
+              qkv.sizes(), " and a suffix cache ", ks.sizes(), " do not match ", n, " samples for each group of a ",
+              kp.sizes(), " prefix cache");
+  TORCH_CHECK(Pmax >= 1 && Nmax >= 1, "attention_fork: empty caches");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && aligned16(qkv), "attention_fork: 16-byte aligned rows required");
+  TORCH_CHECK(plens.device() == qkv.device() && lens.device() == qkv.device(),
+              "attention_fork: all tensors on one device");
+  TORCH_CHECK(plens.scalar_type() == torch::kInt32 && plens.is_contiguous() && plens.dim() == 1 && plens.numel() == G,
+              "attention_fork: plens must be int32 [G] on the device");
+  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() && lens.dim() == 1 && lens.numel() == R,
+              "attention_fork: lens must be int32 [R] on the device");
+  TORCH_CHECK(n_keys >= 1 && n_keys <= Pmax + Nmax, "attention_fork: n_keys = ", n_keys, " outside 1..", Pmax + Nmax,
+              " (the prefix cache's rows plus the suffix cache's)");
+  TORCH_CHECK(R <= 65535 && H >= 1 && H <= 65535, "attention_fork: rows / heads out of the grid's range");
+  sdml::AttnForkArgs a;
+  a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
+  auto out = torch::empty({R, C}, qkv.options());
+  auto ws = torch::empty({R * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
+  a.qkv = qkv.data_ptr(), a.k_prefix = kp.data_ptr(), a.v_prefix = vp.data_ptr();
+  a.k_suffix = ks.data_ptr(), a.v_suffix = vs.data_ptr(), a.out = out.data_ptr();
+  a.plens = plens.data_ptr<int>(), a.lens = lens.data_ptr<int>();
+  a.ws_o = ws.data_ptr<float>();
+  a.ws_ml = a.ws_o + R * H * a.max_chunks * 64;
+  a.G = (int)G, a.n = (int)n, a.H = (int)H, a.Pmax = (int)Pmax, a.Nmax = (int)Nmax, a.n_keys = (int)n_keys;
+  a.ldq = qkv.stride(0);
+  a.psb = kp.stride(0), a.pss = kp.stride(1), a.psh = kp.stride(2);
+  a.ssb = ks.stride(0), a.sss = ks.stride(1), a.ssh = ks.stride(2);
+  a.scale = (float)scale;
+  sdml::attention_fork_bf16(a, cur_stream());
+  return out;
+}
+
 // Prompt-lookup speculation's accept + draft (kernels.h LookupStepArgs; ops/reference.py lookup_step). g, tok_in
 // int64 [B, K + 1] and nq_in int32 [B], or all three None: nothing to accept. out int64 [B, W]; lens, limit, done,
 // gen_len, row_steps int32 [B]. Returns (tok_next int64 [B, K + 1], nq_next int32 [B], all_done int32 [1]).
@@ -2461,6 +2520,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "positions' k, v at rows lens[b] + t, returns [B, T, C] with attention_fwd's bits per position",
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("nq"), py::arg("scale"),
         py::arg("n_keys"));
+  m.def("attention_fork", &attention_fork,
+        "one new token for each of G n rows, n siblings sharing a group's prefix cache (bf16, d=64): writes k, v at "
+        "suffix row lens[r] - plens[g], returns [G n, C] with attention_decode's bits per row",
+        py::arg("qkv"), py::arg("kp"), py::arg("vp"), py::arg("plens"), py::arg("ks"), py::arg("vs"), py::arg("lens"),
+        py::arg("n"), py::arg("scale"), py::arg("n_keys"));
   m.def("lookup_step", &lookup_step,
         "prompt-lookup speculation: accept the verify step's drafts, draft the next step's tokens (one launch)",
         py::arg("g"), py::arg("tok_in"), py::arg("nq_in"), py::arg("out"), py::arg("lens"), py::arg("limit"),

@@ -14,8 +14,10 @@ whether all rows have ended). With ``--ragged`` or ``--eos_token`` a printed lin
 length. ``--graph`` replays one captured decode step per token (one rank on a ROCm device, bf16, head width 64; the
 same tokens). ``--lookup K --lookup_ngram N`` is prompt-lookup speculation (one rank): every step verifies K tokens
 drafted from the row's own history, matched on its last N tokens; the same tokens in fewer steps, and ``--stop_check``
-then counts verify steps. ``--metrics`` gets one ``generate`` event: the tokens really generated, seconds, tokens/s,
-graph, lookup, lookup_ngram, steps and tokens per step.
+then counts verify steps. ``--num_samples N`` prints N continuations of every prompt, the N lines of the first prompt
+first (one rank; the prompt is prefilled and its keys are stored once). ``--metrics`` gets one ``generate`` event: the
+tokens really generated over all rows, seconds, tokens/s, graph, lookup, lookup_ngram, steps, tokens per step and
+num_samples.
 """
 from __future__ import annotations
 
@@ -83,6 +85,9 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--prefill_chunk", type=int, default=0, metavar="N",
                    help="prefill the prompt in chunks of N positions through the extend-attention path (0: one pass; "
                         "one rank, not with --graph or --lookup)")
+    s.add_argument("--num_samples", type=int, default=1, metavar="N",
+                   help="N continuations of every prompt from one prefill and one copy of the prompt's keys (1..64; "
+                        "above 1: one rank, not with --graph, --lookup or --prefill_chunk)")
     return p
 
 
@@ -155,7 +160,7 @@ def run(args) -> dict:
                        top_k=args.top_k, seed=args.seed, top_p=args.top_p, prompt_lens=plens,
                        eos_token=args.eos_token, pad_token=args.pad_token, stop_check=args.stop_check,
                        return_lengths=True, graph=args.graph, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
-                       return_stats=not args.graph, prefill_chunk=args.prefill_chunk)
+                       return_stats=not args.graph, prefill_chunk=args.prefill_chunk, num_samples=args.num_samples)
         out, lengths = res[0], res[1]
         steps = res[2]["steps"] if len(res) > 2 else None
         rows = out.cpu().tolist()  # (the read-back ends the timed region)
@@ -166,15 +171,16 @@ def run(args) -> dict:
         raise SystemExit(str(e))
     if plens is not None or args.eos_token is not None or args.lookup:  # each row up to its own length
         rows = [r[:n] for r, n in zip(rows, lengths)]
-    n_prompt = len(rows) * prompts.shape[1] if plens is None else int(plens.sum())
-    n_new = sum(lengths) - n_prompt  # the tokens really generated (the eos included)
+    n_prompt = len(rows) * prompts.shape[1] if plens is None else int(plens.sum()) * args.num_samples
+    n_new = sum(lengths) - n_prompt  # the tokens really generated (the eos included), over all rows
     if mesh.is_master():
         for r in rows:
             print(",".join(str(t) for t in r), flush=True)
         metrics.log(event="generate", samples=len(rows), prompt_len=prompts.shape[1], tokens=n_new, seconds=dt_s,
                     tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k,
                     top_p=args.top_p, graph=bool(args.graph), lookup=args.lookup, lookup_ngram=args.lookup_ngram,
-                    steps=steps, tokens_per_step=None if not steps else n_new / steps)
+                    steps=steps, tokens_per_step=None if not steps else n_new / steps,
+                    num_samples=args.num_samples)
     return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
 
 

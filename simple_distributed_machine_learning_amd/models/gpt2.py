@@ -29,8 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .base import ModelSpec, PipelineStage
-from ..ops.decode import (ATTENTION_APPEND_MAX_T, LINEAR_DECODE_MAX_M, attention_append, attention_decode,
-                          attention_extend, embedding_at, linear_decode)
+from ..ops.decode import (ATTENTION_APPEND_MAX_T, ATTENTION_FORK_MAX_N, LINEAR_DECODE_MAX_M, attention_append,
+                          attention_decode, attention_extend, attention_fork, embedding_at, linear_decode)
 from ..ops.linear import Linear, _w_padded, linear, lm_head, mlp_gelu
 from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
                              dropout_threshold)
@@ -322,7 +322,7 @@ class GPT2Stage(PipelineStage):
         return linear_decode(y, w if wp is None else wp)
 
     @torch.no_grad()
-    def prefill(self, x, cache: "KVCache", lens=None):
+    def prefill(self, x, cache: "KVCache", lens=None, head_rows: int = 1):
         """The prompt through this stage: today's forward (flash attention at the prompt length, no dropout) plus the
         copies of every layer's k / v into the cache. x: tokens [B, S0] on stage 0, else [B, S0, C]. Returns the
         boundary [B, S0, C], or on the last stage the logits [B, ld] of the last position only.
@@ -331,7 +331,12 @@ class GPT2Stage(PipelineStage):
         right-padded to S0. Causal attention keeps every position < lens[b] independent of the padding, and the cache
         rows >= lens[b] are never read by the decode attention (each is overwritten before its turn). The cache
         lengths become ``lens``, ``cache.n`` = S0 bounds the longest row, and the last stage returns the logits of
-        position lens[b] - 1 of each sample (a gather on the device)."""
+        position lens[b] - 1 of each sample (a gather on the device).
+
+        ``head_rows`` = n > 1 (``generate(num_samples=n)``): the last stage returns [B n, ld], sample b's logits in
+        rows b n .. b n + n - 1. The sample's last hidden row is repeated ahead of the lm_head, not the logits after
+        it, so the head runs over B n rows through the entry point that the prefill of the n-fold repeated prompts
+        takes (``linear_decode`` up to 64 rows, the GEMM beyond) and the rows carry that call's bits."""
         if self.stage_id == 0:
             x = embedding(x, self.wte.weight, self.wpe.weight)
         B, S, C = x.shape
@@ -365,9 +370,11 @@ class GPT2Stage(PipelineStage):
             return x
         if y is None:
             y = self.ln_f(x)
-        if lens is None:
+        if lens is None and head_rows == 1:
             return self._head_logits(y[:, -1].contiguous())
         rows = torch.arange(B, device=y.device) * S + (cache.lens.to(torch.int64) - 1)
+        if head_rows > 1:
+            rows = rows.repeat_interleave(int(head_rows))
         return self._head_logits(y.reshape(B * S, C).index_select(0, rows))
 
     @torch.no_grad()
@@ -461,6 +468,64 @@ class GPT2Stage(PipelineStage):
                 x, y = add_layer_norm(x, m, nxt)
         cache.lens.add_(1)
         cache.n += 1
+        if not last:
+            return x
+        if y is None:
+            y = self.ln_f(x)
+        return self._head_logits(y)
+
+    def fork_cache(self, cache: "KVCache", n_samples: int, nmax: int) -> "ForkedKVCache":
+        """n_samples continuations of every prompt of a prefilled ``cache``: the cache itself becomes the shared
+        prefix (its ``lens`` are the prompt lengths; it is only read from here on), and every row b n + j, sibling j
+        of prompt b, gets ``nmax`` suffix positions of its own per local layer. ``cache.n + nmax`` may not exceed
+        block_size."""
+        if isinstance(n_samples, bool) or not isinstance(n_samples, int) or not 1 <= n_samples <= ATTENTION_FORK_MAX_N:
+            raise ValueError(f"fork_cache: n_samples must be an integer in 1..{ATTENTION_FORK_MAX_N}, got {n_samples!r}")
+        if cache.n < 1:
+            raise ValueError("fork_cache: the cache holds no prompt; prefill it first")
+        if nmax < 1 or cache.n + nmax > self.cfg.block_size:
+            raise ValueError(f"fork_cache: {cache.n} prompt positions + nmax = {nmax} must lie in {cache.n + 1}.."
+                             f"block_size={self.cfg.block_size}")
+        R = cache.lens.shape[0] * n_samples
+        mk = lambda t: torch.empty((R, nmax) + t.shape[2:], dtype=t.dtype, device=t.device)  # noqa: E731
+        return ForkedKVCache(cache, [mk(t) for t in cache.k], [mk(t) for t in cache.v],
+                             cache.lens.repeat_interleave(n_samples), n_samples, cache.n, int(nmax))
+
+    @torch.no_grad()
+    def decode_step_forked(self, x, fc: "ForkedKVCache"):
+        """``decode_step`` over the B n rows of a forked cache: one new token per row, x tokens [B n] on stage 0, else
+        [B n, C]. The lines are ``decode_step``'s with ``attention_fork`` at the attention site, which reads a
+        prompt's keys once for its n siblings; every other kernel of the step computes a row from that row alone, so
+        a row's bits are those of ``decode_step`` on the n-fold repeated batch (docs/NUMERICS.md). Appends the
+        token's k / v to the row's suffix, advances ``fc.lens`` and ``fc.n``; returns [B n, C] or on the last stage
+        the logits [B n, ld]."""
+        if fc.n + 1 - fc.prefix.n > fc.nmax:
+            raise ValueError(f"the forked cache is full ({fc.n - fc.prefix.n} of {fc.nmax} suffix positions)")
+        if self.stage_id == 0:
+            x = embedding_at(x, fc.lens, self.wte.weight, self.wpe.weight)
+        last = self.stage_id == self.num_stages - 1
+        blocks = list(self.h.values())
+        H = self.cfg.n_head
+        pre = fc.prefix
+        y = None
+        if blocks:
+            x, y = layer_norm_pass(x, blocks[0].ln_1)
+        for i, blk in enumerate(blocks):
+            at, mlp = blk.attn, blk.mlp
+            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias)
+            a = attention_fork(qkv, pre.k[i], pre.v[i], pre.lens, fc.ks[i], fc.vs[i], fc.lens, fc.n_samples, H,
+                               fc.n + 1)
+            a = linear_decode(a, at.c_proj.weight, at.c_proj.bias)
+            x, y = add_layer_norm(x, a, blk.ln_2)
+            m = linear_decode(linear_decode(y, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True), mlp.c_proj.weight,
+                              mlp.c_proj.bias)
+            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
+            if nxt is None:
+                x = x + m
+            else:
+                x, y = add_layer_norm(x, m, nxt)
+        fc.lens.add_(1)
+        fc.n += 1
         if not last:
             return x
         if y is None:
@@ -584,6 +649,21 @@ class KVCache:
     n: int
     smax: int
     tickets: Optional[torch.Tensor] = None  # new_cache(fused=True): the arrival counters of decode_step(fused=True)
+
+
+@dataclass
+class ForkedKVCache:
+    """n_samples continuations of every prompt of a prefilled cache (``GPT2Stage.fork_cache``): ``prefix`` is that
+    cache of B rows, read only, its ``lens`` the prompt lengths; ``ks`` / ``vs`` per local layer [B n_samples, nmax,
+    H, D] hold each row's own later keys, row b n_samples + j being sibling j of prompt b; ``lens`` int32 [B
+    n_samples] on the device = prompt plus suffix keys cached per row; ``n`` the host's bound on them."""
+    prefix: KVCache
+    ks: list
+    vs: list
+    lens: torch.Tensor
+    n_samples: int
+    n: int
+    nmax: int
 
 
 def gpt2_spec(num_stages: int = 2, cfg: GPT2Config = None, seq_len: int = None, dtype=torch.bfloat16,

@@ -1,5 +1,5 @@
 """Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, attention_append.hip,
-attention_extend.hip, linear_decode.hip, sample.hip, lookup.hip) and their torch twins.
+attention_extend.hip, attention_fork.hip, linear_decode.hip, sample.hip, lookup.hip) and their torch twins.
 
 Dispatch: ROCm bf16 tensors (head width 64 for the attention) run the hand-written kernels, and a shape the kernels do
 not take is an error there, never a library call. CPU tensors, fp32 and other head widths run the twins below, which
@@ -18,6 +18,7 @@ from . import reference as _ref
 EPI_STORE, EPI_BIAS, EPI_BIAS_GELU = 0, 1, 5  # csrc/kernels/kernels.h GemmEpi
 LINEAR_DECODE_MAX_M = 64  # kLinearDecodeMaxM
 ATTENTION_APPEND_MAX_T = 8  # kAttnAppendMaxT
+ATTENTION_FORK_MAX_N = 64  # kAttnForkMaxN
 LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM = 7, 8  # kLookupMaxDrafts, kLookupMaxNgram
 
 
@@ -203,6 +204,77 @@ def attention_extend(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
     if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
         return kernels().attention_extend(qkv, k_cache, v_cache, lens, nq, 1.0 / math.sqrt(D), int(n_keys))
     return attention_extend_ref(qkv, k_cache, v_cache, lens, nq, n_head, n_keys)
+
+
+def attention_fork_ref(qkv, kp, vp, plens, ks, vs, lens, n: int, n_head: int, n_keys: int):
+    """The twin of ``attention_fork``: materialise each row's cache, the group's ``plens[g]`` prompt rows followed by
+    the row's ``lens[r] - plens[g]`` suffix rows, run ``attention_decode_ref`` on it with ``lens[r]`` keys cached, and
+    write the new k, v to suffix row ``lens[r] - plens[g]``. Rows the token does not see are zeros in the materialised
+    cache (the tails of both caches may hold NaN patterns)."""
+    R = qkv.shape[0]
+    Pmax, Nmax = kp.shape[1], ks.shape[1]
+    C = qkv.shape[1] // 3
+    rows = torch.arange(R, device=qkv.device)
+    grp = rows // int(n)
+    pl, ln = plens.to(torch.int64)[grp], lens.to(torch.int64)
+    i = torch.arange(Pmax + Nmax, device=qkv.device)[None, :]  # key index
+    from_p, from_s = i < pl[:, None], (i >= pl[:, None]) & (i < ln[:, None])
+    ip = i.clamp(max=Pmax - 1).expand(R, -1)
+    is_ = (i - pl[:, None]).clamp(0, Nmax - 1)
+    caches = []
+    for pre, suf in ((kp, ks), (vp, vs)):
+        both = torch.where(from_p[:, :, None, None], pre[grp[:, None], ip],
+                           torch.where(from_s[:, :, None, None], suf[rows[:, None], is_],
+                                       torch.zeros((), dtype=suf.dtype, device=suf.device)))
+        caches.append(both)
+    out = attention_decode_ref(qkv, caches[0], caches[1], lens, n_head, n_keys)
+    ks[rows, ln - pl] = qkv[:, C:2 * C].view(R, n_head, -1)
+    vs[rows, ln - pl] = qkv[:, 2 * C:].view(R, n_head, -1)
+    return out
+
+
+def attention_fork(qkv, kp, vp, plens, ks, vs, lens, n: int, n_head: int, n_keys: int):
+    """One new token for each of R = G n rows, n continuations per prompt (attention_fork.hip). Row g n + j is sibling
+    j of group g. qkv [R, 3C]: the tokens' fused projections; ``kp`` / ``vp`` [G, Pmax, H, D] with ``plens`` int32 [G]
+    on the device: the groups' prompt keys, stored once and only read; ``ks`` / ``vs`` [R, Nmax, H, D]: every row's own
+    later keys; ``lens`` int32 [R] on the device: ``plens[g]`` plus the row's suffix keys. Key i of row r is
+    ``kp[g, i]`` for i < plens[g], ``ks[r, i - plens[g]]`` up to lens[r], and the row's own ``qkv`` at i == lens[r],
+    which is written to suffix row lens[r] - plens[g]. Returns [R, C], bit for bit on the kernels what
+    ``attention_decode`` returns for that token on a cache holding the prompt rows followed by the suffix rows; the
+    kernel loads a 64-key chunk of the prompt once for the n siblings. ``n_keys`` is the host's bound lens[r] + 1 <=
+    n_keys <= Pmax + Nmax, or a ValueError; ``lens`` and ``plens`` are not changed."""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= ATTENTION_FORK_MAX_N:
+        raise ValueError(f"attention_fork: n must be an integer in 1..{ATTENTION_FORK_MAX_N} (samples per group), got "
+                         f"{n!r}")
+    ts = (qkv, kp, vp, ks, vs)
+    if _hip_bf16(*ts) and kp.dim() == 4 and kp.shape[-1] == 64 and kp.shape[2] == n_head:
+        # the kernel path: the binding checks every argument (the decode loop calls this once per layer and step, so
+        # nothing is checked twice); its refusals name the function and leave here as ValueError, like the twin path's
+        try:
+            return kernels().attention_fork(qkv, kp, vp, plens, ks, vs, lens, n, 1.0 / math.sqrt(64), int(n_keys))
+        except RuntimeError as e:
+            if not str(e).startswith("attention_fork:"):
+                raise
+            raise ValueError(str(e).split("\n")[0]) from None
+    if qkv.dim() != 2 or kp.dim() != 4 or ks.dim() != 4 or kp.shape != vp.shape or ks.shape != vs.shape or \
+            kp.shape[2:] != ks.shape[2:] or kp.shape[2] != n_head or qkv.shape[1] != 3 * kp.shape[2] * kp.shape[3] or \
+            qkv.shape[0] != kp.shape[0] * n or ks.shape[0] != qkv.shape[0] or kp.shape[1] < 1 or ks.shape[1] < 1:
+        raise ValueError(f"attention_fork: qkv must be [G n, 3C] against prefix caches [G, Pmax, H, D] and suffix "
+                         f"caches [G n, Nmax, H, D] with C = H D, got {tuple(qkv.shape)}, {tuple(kp.shape)}, "
+                         f"{tuple(vp.shape)}, {tuple(ks.shape)}, {tuple(vs.shape)}, n={n}, n_head={n_head}")
+    if any(t.dtype != qkv.dtype for t in ts) or any(t.device != qkv.device for t in ts + (plens, lens)):
+        raise ValueError(f"attention_fork: qkv and the caches must share one dtype, and all tensors one device, got "
+                         f"{[str(t.dtype) for t in ts]} on {[str(t.device) for t in ts + (plens, lens)]}")
+    if kp.stride() != vp.stride() or ks.stride() != vs.stride():
+        raise ValueError("attention_fork: kp / vp and ks / vs must each share one layout, got strides "
+                         f"{kp.stride()}, {vp.stride()}, {ks.stride()}, {vs.stride()}")
+    G, Pmax, Nmax = kp.shape[0], kp.shape[1], ks.shape[1]
+    if not 1 <= n_keys <= Pmax + Nmax:
+        raise ValueError(f"attention_fork: n_keys = {n_keys}, but the caches have {Pmax} + {Nmax} rows")
+    for name, t, want in (("plens", plens, G), ("lens", lens, G * n)):
+        if t.dtype != torch.int32 or t.shape != (want,):
+            raise ValueError(f"attention_fork: {name} must be int32 [{want}], got {t.dtype} {tuple(t.shape)}")
+    return attention_fork_ref(qkv, kp, vp, plens, ks, vs, lens, n, n_head, n_keys)
 
 
 def lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, k: int, ngram: int, eos: int = -1,

@@ -39,6 +39,14 @@ extend-attention kernel) and then decodes as always; it runs on a ``GenerationSe
 also how a cache outlives a call: more tokens, the next turn, appended tokens. It is refused with ``graph=True`` and
 with ``lookup > 0``.
 
+``num_samples=n`` (2..64, one rank) returns n continuations of every prompt, ``[B n, S0 + max_new_tokens]`` with row
+``b n + j`` sibling j of prompt b. The prompts are prefilled once; every stage's cache is forked (models/gpt2.py
+``fork_cache``: the prefilled cache stays as the shared prefix, each row gets ``max_new_tokens`` suffix positions) and
+the B n rows decode through ``decode_step_forked``, whose attention (attention_fork.hip) reads a prompt's keys once
+for its n siblings. Row ``b n + j`` is the sampler's sample ``sample0 + b n + j``, so siblings draw different noise, and
+tokens, lengths and stats are those of the call on ``prompts.repeat_interleave(n, 0)`` bit for bit (docs/NUMERICS.md).
+It is refused with ``graph=True``, ``lookup > 0``, ``prefill_chunk > 0`` and pp > 1.
+
 Limitations: tensor parallelism, data parallelism and ``--schedule rotate`` are refused. With pp ranks one rank works
 at a time (a token must leave the last stage before stage 0 can embed it); several sample groups in flight would fill
 the bubble and are not implemented. ``graph=True`` is refused with pp > 1: the step's boundaries cross ranks between
@@ -52,7 +60,8 @@ from typing import Optional
 
 import torch
 
-from ..ops.decode import LINEAR_DECODE_MAX_M, LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, lookup_step, sample_logits, sample_step
+from ..ops.decode import (ATTENTION_FORK_MAX_N, LINEAR_DECODE_MAX_M, LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, lookup_step,
+                          sample_logits, sample_step)
 
 # message tags no schedule produces: message_tag() keeps mb * 4096 + stage in the bits above 2, and a schedule's
 # stage index is far below 4095
@@ -165,12 +174,89 @@ def _generate_chunked(engine, prompts, new, temperature, top_k, seed, sample0, t
     return res
 
 
+def _check_samples(engine, num_samples, graph: bool, lookup: int, prefill_chunk: int):
+    """The refusals of ``num_samples``."""
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or \
+            not 1 <= num_samples <= ATTENTION_FORK_MAX_N:
+        raise ValueError(f"generate: num_samples must be an integer in 1..{ATTENTION_FORK_MAX_N}, got {num_samples!r}")
+    if num_samples == 1:
+        return
+    for on, what in ((graph, "graph=True (the forked step is not captured yet)"),
+                     (lookup > 0, "lookup > 0 (the verify step does not read a shared prefix yet)"),
+                     (prefill_chunk > 0, "prefill_chunk > 0 (a session cannot be forked yet)"),
+                     (engine.mesh.pp > 1, f"pp={engine.mesh.pp} (the fork does not cross pipeline ranks yet); run one "
+                                          "rank")):
+        if on:
+            raise ValueError(f"generate: num_samples > 1 is not supported with {what}")
+
+
+def _generate_forked(engine, prompts, cfg, new: int, temperature, top_k, nseed: int, sample0: int, top_p, lens_host,
+                     eos_token, pad_token, stop_check, return_lengths: bool, return_stats: bool, n: int):
+    """generate() with ``num_samples`` = n > 1 (one rank): the B prompts are prefilled once, every local stage's cache
+    is forked (models/gpt2.py fork_cache) and the B n rows decode through ``decode_step_forked``. Row b n + j is
+    sibling j of prompt b and sample ``sample0 + b n + j`` of the sampler, so tokens, lengths and stats are those of
+    the call on ``prompts.repeat_interleave(n, 0)``, bit for bit: the sampler lines below are that call's."""
+    dev, P = engine.device, engine.P
+    B, S0 = prompts.shape
+    R, total = B * n, S0 + new
+    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0
+    prompts = prompts.to(dev)
+    lens_b = torch.tensor(lens_host if lens_host is not None else [S0] * B, dtype=torch.int64, device=dev)
+    if stepped:  # (the padding holds the pad token, whatever the caller left there)
+        prompts = torch.where(torch.arange(S0, device=dev)[None, :] < lens_b[:, None], prompts,
+                              torch.full_like(prompts, int(pad_token)))
+    lens0 = lens_b.repeat_interleave(n)
+    out = torch.full((R, total), int(pad_token), dtype=torch.int64, device=dev)
+    out[:, :S0] = prompts.repeat_interleave(n, 0)
+    done = torch.zeros(R, dtype=torch.int32, device=dev)
+    gen_len = torch.zeros(R, dtype=torch.int32, device=dev)
+    eos = -1 if eos_token is None else int(eos_token)
+    check = int(stop_check) if eos_token is not None else 0
+    steps_run = 0
+    if new > 0:
+        stages = [engine.stages[s] for s in range(P)]
+        was_training = [m.training for m in stages]
+        for m in stages:
+            m.eval()
+        try:
+            lens_dev = lens_b.to(torch.int32) if lens_host is not None else None
+            caches = [m.new_cache(B, S0) for m in stages]  # the shared prefixes: the prompt's rows and no more
+            x = prompts
+            for s, m in enumerate(stages):
+                x = m.prefill(x, caches[s], lens=lens_dev, head_rows=n if s == P - 1 else 1)
+            forks = [m.fork_cache(caches[s], n, new) for s, m in enumerate(stages)]
+            lens = forks[P - 1].lens
+            for t in range(new):  # token index S0 + t (ragged: lens[r] + t)
+                if t > 0:
+                    for s, m in enumerate(stages):
+                        x = m.decode_step_forked(x, forks[s])
+                if stepped:
+                    x = sample_step(x, cfg.vocab_size, temperature, top_k, top_p, nseed, sample0, lens, out, done,
+                                    gen_len, eos, int(pad_token))
+                else:
+                    x = sample_logits(x, cfg.vocab_size, temperature, top_k, nseed, sample0, lens)
+                    out[:, S0 + t] = x
+                if check and (t + 1) % check == 0 and t + 1 < new and bool(done.min().item()):
+                    break
+            steps_run = t + 1
+        finally:
+            for m, tr_ in zip(stages, was_training):
+                m.train(tr_)
+    lengths = lens0 + gen_len if stepped else torch.full((R,), total, dtype=torch.int64, device=dev)
+    res = (out, lengths) if return_lengths else out
+    if return_stats:
+        generated = lengths - lens0 if stepped else torch.full((R,), new, dtype=torch.int64, device=dev)
+        stats = {"steps": steps_run, "row_steps": generated.clone(), "generated": generated}
+        res = (res if isinstance(res, tuple) else (res,)) + (stats,)
+    return res
+
+
 @torch.no_grad()
 def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              seed: Optional[int] = None, sample0: int = 0, top_p: float = 1.0, prompt_lens=None,
              eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
              graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False,
-             prefill_chunk: int = 0):
+             prefill_chunk: int = 0, num_samples: int = 1):
     """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
     ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
     samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
@@ -186,7 +272,10 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     host's loop count), ``row_steps`` and ``generated`` (int64 [B] on the device: the steps in which the row emitted a
     token, and its generated tokens). ``prefill_chunk`` = P > 0 (one rank, not with ``graph`` or ``lookup``): the prompt
     goes through ``extend`` in chunks of P positions instead of one ``prefill`` pass, on a ``GenerationSession``
-    (parallel/session.py) that lives for this call; 0 runs the lines it always ran."""
+    (parallel/session.py) that lives for this call; 0 runs the lines it always ran. ``num_samples`` = n in 2..64 (one
+    rank, not with ``graph``, ``lookup`` or ``prefill_chunk``): n continuations of every prompt from one prefill and
+    one copy of the prompt's keys; the result has B n rows, row b n + j sibling j of prompt b, and is that of the call
+    on ``prompts.repeat_interleave(n, 0)`` bit for bit (module docstring); 1 runs the lines it always ran."""
     from ..models.gpt2 import dropout_seed
 
     prompts, cfg = _check(engine, prompts, int(max_new_tokens))
@@ -201,6 +290,11 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
                          "prefill runs on a session, which neither path drives yet)")
     if return_stats and graph:
         raise ValueError("generate: return_stats is not available with graph=True")
+    _check_samples(engine, num_samples, graph, lookup, prefill_chunk)
+    if num_samples > 1:
+        return _generate_forked(engine, prompts, cfg, int(max_new_tokens), temperature, top_k,
+                                dropout_seed(0 if seed is None else seed), sample0, top_p, lens_host, eos_token,
+                                pad_token, stop_check, return_lengths, return_stats, num_samples)
     if prefill_chunk > 0:
         return _generate_chunked(engine, prompts, int(max_new_tokens), temperature, top_k, seed, sample0, top_p,
                                  lens_host, eos_token, pad_token, stop_check, return_lengths, return_stats,
