@@ -384,9 +384,12 @@ __global__ void __launch_bounds__(256) head_lds_kernel(const float* __restrict__
 #pragma unroll
         for (int c = 0; c < C; ++c) {
           const float4 w = Ws4[c * nch + ch];
+          // one explicit fma chain per (row, class): every class runs the same roundings whatever the compiler pairs
+          // into packed instructions, so identical rows of W give bit-equal logits and a tie goes to the first index
+          // (written as a sum of products, the contraction differed between classes: tests/test_mlp_numerics_gpu.py)
 #pragma unroll
           for (int rr = 0; rr < R; ++rr)
-            z[rr][c] += xv[rr][j].x * w.x + xv[rr][j].y * w.y + xv[rr][j].z * w.z + xv[rr][j].w * w.w;
+            z[rr][c] = fmaf(xv[rr][j].w, w.w, fmaf(xv[rr][j].z, w.z, fmaf(xv[rr][j].y, w.y, fmaf(xv[rr][j].x, w.x, z[rr][c]))));
         }
     }
     float dz[R][C];
