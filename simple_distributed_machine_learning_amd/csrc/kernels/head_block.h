@@ -16,10 +16,13 @@
 // slower per product) and cost ~12K of the fused forward's ~27K-cycle epilogue per block.
 //
 // Block = 8 waves, wave w = (wm = w % 4, wn = w / 4) holding h[64 wm + ..][64 wn + ..] in the 32x32 MFMA C
-// layout: y[i][j][r] = h[64 wm + 32 i + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)][64 wn + 32 j + (lane & 31)].
+// layout: y[i][j][r] = h[64 wm + 32 i + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)][64 wn + 32 j + (lane & 31)] (Map32: the
+// standalone head), or in the 16x16 one: y[t][c][v] = h[64 wm + 16 t + 4 (lane >> 4) + v][64 wn + 16 c + (lane & 15)]
+// (Map16: the fused uint8 forward's accumulators). Only the block max |h| and the h image's writes look at y; the image
+// bytes for a given h are the same from either layout, and everything after reads the image.
 //  1. h planes into an LDS image [plane][hid][row] of 8-byte granules (4 rows of one hidden unit): the C
 //     layout gives a lane exactly one granule per register quad, so the image is written with 32
-//     ds_write_b64 per lane (round 4: 64 ds_write_b32 of fp32). Granule q of hidden unit h sits at q ^ gswz(h):
+//     ds_write_b64 per lane in either layout (round 4: 64 ds_write_b32 of fp32). Granule q of hidden unit h sits at q ^ gswz(h):
 //     the writes (16 lanes = 16 hidden units), the logits' transposed reads and the dW2 reads are all
 //     bank-conflict-free (checked by enumeration in tests/test_head_block_layout.py).
 //  2. logits^T = W2 h^T, 16 classes x 16 rows per 16x16x32 MFMA: A = W2 planes (lane: class), B = the h image
@@ -31,6 +34,8 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "head_tile.h"
 #include "lds_dma.h"
@@ -155,6 +160,10 @@ __device__ __forceinline__ void load_operands(const Args& a, int m0, int M, int 
     o.tg[it] = reinterpret_cast<const int*>(a.target)[2 * (size_t)min(m0 + 16 * (wave + NW * it) + r, M - 1)];
 }
 
+// the wave tile's register layout handed to block_head (see the top of the file): y is hb_f32x16[2][2] or hb_f32x4[4][4]
+struct Map32 {};
+struct Map16 {};
+
 // prep(y) fills y: this wave's 64 x 64 tile of h (rows >= M zero), C layout above. smem: LDS_BYTES, free (the caller's
 // previous use finished with a barrier or not yet started: the first thing here is a barrier). hook(T, row, valid, dz):
 // called per row tile after the softmax with the lane's dz (the standalone head's dx pass; a no-op when fused).
@@ -162,10 +171,12 @@ struct NoOp {
   __device__ void operator()() const {}
 };
 // post_b1(): run right after the first barrier (the fused forward issues its next-block pixel prefetch there)
-template <int C, class Prep, class Hook, class PostB1 = NoOp>
+template <int C, class Prep, class Hook, class PostB1 = NoOp, class Map = Map32>
 __device__ __forceinline__ void block_head(Prep&& prep, unsigned char* smem, const Args& a, const Operands& ops, int m0,
                                            int M, int wave, int lane, Hook&& hook, long long* stamp,
-                                           PostB1&& post_b1 = PostB1{}) {
+                                           PostB1&& post_b1 = PostB1{}, Map = Map{}) {
+  constexpr bool M16 = std::is_same<Map, Map16>::value;
+  constexpr int YA = M16 ? 4 : 2, YV = M16 ? 4 : 16;  // y[YA][YA] tiles of YV registers
   static_assert(C >= 2 && C <= 16 && C % 2 == 0, "one 16-class tile; dl stored by class pairs");
   auto st = [&](int k) {
     if (stamp && lane == 0) stamp[k] = (long long)__builtin_amdgcn_s_memtime();
@@ -179,16 +190,16 @@ __device__ __forceinline__ void block_head(Prep&& prep, unsigned char* smem, con
   for (int v = 0; v < 4; ++v) bv[v] = (4 * g + v) < C ? ops.b[v] : 0.f;
   const int tg[2] = {ops.tg[0], ops.tg[1]};
 
-  hb_f32x16 y[2][2];
+  typename std::conditional<M16, hb_f32x4, hb_f32x16>::type y[YA][YA];
   prep(y);
   // block max |h| -> plane scale (all waves, after one exchange)
   float hm = 0.f;
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < YA; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < YA; ++j)
 #pragma unroll
-      for (int q = 0; q < 16; ++q) hm = fmaxf(hm, fabsf(y[i][j][q]));
+      for (int q = 0; q < YV; ++q) hm = fmaxf(hm, fabsf(y[i][j][q]));
   hm = wv::max64(hm);
   // max |W2| over the staged chunks (threads past C * HID / 4 hold a clamped duplicate)
   const float wc = fmaxf(fmaxf(fabsf(ops.w2c[0]), fabsf(ops.w2c[1])), fmaxf(fabsf(ops.w2c[2]), fabsf(ops.w2c[3])));
@@ -225,27 +236,43 @@ __device__ __forceinline__ void block_head(Prep&& prep, unsigned char* smem, con
   // 1. the h image: granule (4 rows) of hidden unit 64 wn + 32 j + r32, rows 64 wm + 32 i + 8 rq + 4 h2 ..
   // granule q = (16 wm + h2) | (8 i + 2 rq): its byte offset hoff(p, hid, q) is a lane base XOR 8 (8 i + 2 rq) (the
   // granule's varying bits 1..3 never carry; the swizzle is lane-constant), one VALU per address
-  const int ib0 = hid_base(64 * wn + r32, 16 * wm + h2), ib1 = hid_base(64 * wn + 32 + r32, 16 * wm + h2);
+  // one granule: the four rows' values v0..v3 of one hidden unit -> both planes at byte offset o = hoff(0, hid, q)
+  auto put = [&](float v0, float v1, float v2, float v3, int o) {
+    // split2's operations, the hi planes on pairs (v_pk_mul_f32, v_cvt_pk_f16_f32) and each lo as one mixed
+    // fma (v_fma_mix{lo,hi}_f16: fp16(x - hi) from the f32 x and the f16 hi): the same IEEE results as the
+    // scalar form in 4 instead of 8 instructions per pair - the epilogue is VALU-bound
+    const hb_f32x2 x01 = hb_f32x2{v0, v1} * sh2;
+    const hb_f32x2 x23 = hb_f32x2{v2, v3} * sh2;
+    const hb_f16x2 h01 = __builtin_convertvector(x01, hb_f16x2), h23 = __builtin_convertvector(x23, hb_f16x2);
+    const hb_f16x4 hi = {h01[0], h01[1], h23[0], h23[1]};
+    const hb_f16x2 l01 = lo_pair(h01, x01), l23 = lo_pair(h23, x23);
+    const hb_f16x4 lo = {l01[0], l01[1], l23[0], l23[1]};
+    *reinterpret_cast<hb_f16x4*>(smem + o) = hi;
+    *reinterpret_cast<hb_f16x4*>(smem + HPL + o) = lo;
+  };
+  if constexpr (M16) {
+    // Map16: tile (t, c) is one granule per lane: hidden unit 64 wn + 16 c + r, rows 64 wm + 16 t + 4 g .., granule
+    // q = (16 wm + g) | 4 t: a lane base per column tile XOR 8 (4 t) (t's bits 2..3 are clear in 16 wm + g and the
+    // swizzle is lane-constant). A 16-lane write group is 16 consecutive hidden units of one granule, as in Map32.
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int c = 0; c < 4; ++c) {
+      const int ib = hoff(0, 64 * wn + 16 * c + r, 16 * wm + g);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-      for (int rq = 0; rq < 4; ++rq) {
-        // split2's operations, the hi planes on pairs (v_pk_mul_f32, v_cvt_pk_f16_f32) and each lo as one mixed
-        // fma (v_fma_mix{lo,hi}_f16: fp16(x - hi) from the f32 x and the f16 hi): the same IEEE results as the
-        // scalar form in 4 instead of 8 instructions per pair - the epilogue is VALU-bound
-        const hb_f32x2 x01 = hb_f32x2{y[i][j][4 * rq], y[i][j][4 * rq + 1]} * sh2;
-        const hb_f32x2 x23 = hb_f32x2{y[i][j][4 * rq + 2], y[i][j][4 * rq + 3]} * sh2;
-        const hb_f16x2 h01 = __builtin_convertvector(x01, hb_f16x2), h23 = __builtin_convertvector(x23, hb_f16x2);
-        const hb_f16x4 hi = {h01[0], h01[1], h23[0], h23[1]};
-        const hb_f16x2 l01 = lo_pair(h01, x01), l23 = lo_pair(h23, x23);
-        const hb_f16x4 lo = {l01[0], l01[1], l23[0], l23[1]};
-        const int o = (j ? ib1 : ib0) ^ (8 * (8 * i + 2 * rq));  // = hoff(0, hid, q)
-        *reinterpret_cast<hb_f16x4*>(smem + o) = hi;
-        *reinterpret_cast<hb_f16x4*>(smem + HPL + o) = lo;
-      }
+      for (int t = 0; t < 4; ++t) put(y[t][c][0], y[t][c][1], y[t][c][2], y[t][c][3], ib ^ (8 * (4 * t)));
     }
+  } else {
+    const int ib0 = hid_base(64 * wn + r32, 16 * wm + h2), ib1 = hid_base(64 * wn + 32 + r32, 16 * wm + h2);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+          const int o = (j ? ib1 : ib0) ^ (8 * (8 * i + 2 * rq));  // = hoff(0, hid, q)
+          put(y[i][j][4 * rq], y[i][j][4 * rq + 1], y[i][j][4 * rq + 2], y[i][j][4 * rq + 3], o);
+        }
+      }
+  }
   __syncthreads();  // (B2) the h image and W2's planes are complete
   st(18);
   // W2 planes (A operands of the logits): lane (class r, k-group g) takes W2[r][32 kk + 8 g .. +7], wp[kk][0] hi, [1] lo

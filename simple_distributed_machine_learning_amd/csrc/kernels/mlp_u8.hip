@@ -10,11 +10,15 @@
 //
 // Accumulation: straight MFMA chains (no per-K-step fp32 partials). tools/probes/mfma_acc_probe.hip
 // measured v_mfma_f32_32x32x16_bf16's accumulation on gfx950 as unbiased and more accurate than a
-// k-ordered fp32 fmaf chain (K = 4096: 2.7e-7 vs 7.6e-7 mean relative error, bias 4e-9).
+// k-ordered fp32 fmaf chain (K = 4096: 2.7e-7 vs 7.6e-7 mean relative error, bias 4e-9), and
+// tools/probes/mfma16_acc_probe.hip the forward's v_mfma_f32_16x16x32_f16 on bytes against the two
+// planes as no worse than the 32x32x16 form (K = 784: rms 1.1e-8 for both, 2.6e-8 for the fmaf chain).
 //
 // Structure (gfx950, wave64): NWR x 2 waves (4 x 2 = 512 threads, or 8 x 2 = 1024 threads for the
-// 512-row blocks of large batches, 4 waves per SIMD), wave tile 32 WMT x 64 = WMT x 2 tiles of
-// v_mfma_f32_32x32x16_f16, block tile 32 WMT NWR x 128, K-step 64 (4 MFMA k-substeps).
+// 512-row blocks of large batches, 4 waves per SIMD), wave tile 32 WMT x 64 = 2 WMT x 4 tiles of
+// v_mfma_f32_16x16x32_f16 (the same cycles as WMT x 2 tiles of 32x32x16, measured for the clock the
+// chip holds under the load: docs/TUNING_NOTES.md "uint8 forward on 16x16x32 MFMAs"), block tile
+// 32 WMT NWR x 128, K-step 64 (2 MFMA k-substeps of 32).
 // Both operands reach LDS by LDS-DMA (global_load_lds_dwordx4, 16 B per lane, no VGPR staging)
 // into a ring of NS stages (the DMA of K-step t+1 flies under K-step t's MFMAs). Measured
 // alternatives (on the 3-plane bf16 form): 32-deep K-steps in a 4-stage ring (3 K-steps in flight),
@@ -25,8 +29,8 @@
 // default for large batches (62-65 vs 66.5-67.3 us for 8 waves of 128 x 64).
 // The LDS images are swizzled on the DMA's per-lane source address (the DMA writes 1 KiB
 // lane-linearly) so the fragment ds_read_b128s are conflict-free; k order inside a K-step is
-// permuted identically for both operands (lane half h, substep s, element j <-> k = 32h + 8s + j),
-// so one 32-byte read per row tile feeds all four substeps of the pixel operand. Bytes are widened to
+// permuted identically for both operands (k-group g = lane >> 4, substep s, element j <-> k = 16g + 8s + j),
+// so one 16-byte read per 16-row tile feeds both substeps of the pixel operand. Bytes are widened to
 // fp16 in registers (a byte permute builds 1024 + b, one packed subtract removes the 1024). The
 // epilogue goes through LDS so every lane stores whole 16-byte row pieces.
 // W is pre-split into zero-padded planes [2][N][Kp] (Kp = K rounded up to FBK), so the K tail needs
@@ -55,14 +59,15 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int FBN = 128;                      // columns per block
-constexpr int FBK = 64;                       // k per K-step (FBK / 16 MFMA k-substeps)
+constexpr int FBK = 64;                       // k per K-step (FBK / 32 MFMA k-substeps)
 constexpr int NS = 2;                         // LDS stages
-constexpr int NSUB = FBK / 16;
+constexpr int NSUB = FBK / 32;
 constexpr int NPL = kU8FwdPlanes;            // fp16 weight planes
 constexpr int B_PLANE = FBN * FBK * 2;        // bytes per fp16 plane per stage
-constexpr int XCH = FBK / 16;                 // 16-B chunks per pixel row (2 or 4)
-constexpr int WCH = FBK / 8;                  // 16-B chunks per weight row (4 or 8)
-static_assert(FBK == 32 || FBK == 64, "swizzles below are written for 32- and 64-deep K-steps");
+constexpr int XCH = FBK / 16;                 // 16-B chunks per pixel row
+constexpr int WCH = FBK / 8;                  // 16-B chunks per weight row
+static_assert(FBK == 64, "the lane map (k-group g = lane >> 4 <-> pixel chunk g) and the swizzles below are written for "
+                         "64-deep K-steps");
 
 // block geometry per WMT = 32-row MFMA tiles per wave and NWR = row waves (the block is NWR x 2
 // waves; wave tile 32 WMT x 64, block 32 WMT NWR x 128). NWR = 4: 512 threads (2 waves per SIMD);
@@ -84,10 +89,17 @@ struct Geo {
   static_assert(SMEM <= 160 * 1024, "LDS");
 };
 
-// swizzled 16-B chunk positions: every 16-lane group of a fragment ds_read_b128 (16 rows, one
-// logical chunk) hits 16 distinct bank groups
-__device__ __forceinline__ int xpos(int r, int c) { return c ^ (XCH == 2 ? (r >> 3) & 1 : (r >> 2) & 3); }
-__device__ __forceinline__ int wpos(int r, int c) { return c ^ (WCH == 4 ? (r >> 2) & 3 : (r >> 1) & 7); }
+// swizzled 16-B chunk positions. A fragment ds_read_b128 has lane (r = lane & 15, g = lane >> 4) read row r of a
+// 16-row tile, chunk g (pixels) or 2 g + s (weights), and is served in four groups of 16 lanes that mix two k-groups:
+// rows {0..3, 12..15} of g = 0 (2) with rows 4..11 of g = 1 (3), and rows 4..11 of g = 0 (2) with the other rows of
+// g = 1 (3). Pixel rows are 64 B, so the four rows of a group with the same r & 3 (one from each row quad) share 4
+// bank groups of 16 B and need 4 distinct positions: the quad's XOR value (-quad) & 3 gives {0, 1, 2, 3} for quads
+// (0, 3) with g and (1, 2) with g ^ 1, either way round. Weight rows are 128 B: the 8 rows of one parity in a group
+// need 8 distinct positions; row pairs {0, 1, 6, 7} take the odd XOR values and {2, 3, 4, 5} the even ones (a chunk
+// differs by 2 between the two k-groups of a lane group, and both sets are closed under ^ 2). Checked by enumeration
+// in tests/test_u8_fwd_layout.py. Both use row bits 1..3 only, so tiles 16 rows apart differ by a constant offset.
+__device__ __forceinline__ int xpos(int r, int c) { return c ^ ((-(r >> 2)) & 3); }
+__device__ __forceinline__ int wpos(int r, int c) { return c ^ ((r & 6) | (((r >> 2) ^ (r >> 3) ^ 1) & 1)); }
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -106,8 +118,12 @@ __device__ __forceinline__ f16x8 widen8h(unsigned lo, unsigned hi) {
   return f16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
-__device__ __forceinline__ f32x16 mfma(f16x8 a, f16x8 b, f32x16 c) {
+__device__ __forceinline__ f32x16 mfma(f16x8 a, f16x8 b, f32x16 c) {  // (the weight gradient kernels)
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+// the forward's: lane (r, g) holds A[row r][k-slots 8 g + j], B[k-slots 8 g + j][column r], C[row 4 g + v][column r]
+__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
 struct FwdParams {
@@ -190,22 +206,22 @@ __device__ __forceinline__ void issue_stage(const FwdParams& p, unsigned char* s
 // TAIL = MFMA substeps of the last K-step (tail_substeps: only those holding k < K; chosen on the
 // host so the kernel carries one straight-line tail)
 template <int C, int NWR>
-__device__ __forceinline__ void fused_head_epilogue(const FwdParams& p, const f32x16 (&acc)[2][2], unsigned char* smem,
+__device__ __forceinline__ void fused_head_epilogue(const FwdParams& p, const f32x4 (&acc)[4][4], unsigned char* smem,
                                                     int m0, int wave, int lane, int wm, int wn,
-                                                    const hblk::Operands& ops, const float (&bv1)[2], long long* stamp,
+                                                    const hblk::Operands& ops, const float (&bv1)[4], long long* stamp,
                                                     int hb);
 template <int C>
 __device__ __forceinline__ void fused_head_prefetch(const FwdParams& p, int m0, int wave, int lane, int wn,
-                                                    hblk::Operands& ops, float (&bv1)[2]);
+                                                    hblk::Operands& ops, float (&bv1)[4]);
 
 // HEADC = 0: store h = act(scale acc + b) (+ its ReLU bits when p.mask); HEADC = C > 0: the fused
 // classifier head on h (fused_head_epilogue), h is never stored
 // NSK: LDS ring stages. The fused-head variant may take 3 (the head epilogue needs 148 KiB anyway, so a third
 // 48 KiB stage costs no occupancy: two K-steps of pixel DMA in flight instead of one).
 // DMAS: 0 = the next stage's DMA issued right after the K-step's barrier (all pieces before the first MFMA), 1 = spread
-// over the first substeps (two pieces after each substep's MFMAs: the issue cost of a piece hides under MFMAs instead
-// of delaying the first ones; knob U8_FWD_DMA_SPREAD, NS == 2 only), 2 = 1 + each substep's fragments read one substep
-// ahead
+// over the first three half-substeps (two pieces after every second column tile's MFMAs: the issue cost of a piece
+// hides under MFMAs instead of delaying the first ones; knob U8_FWD_DMA_SPREAD, NS == 2 only), 2 = 1 + each column
+// tile's weight fragments read one tile ahead
 template <int MODE, int WMT, int TAIL, int NWR, int HEADC = 0, int NSK = NS, int DMAS = 0>
 __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(FwdParams p) {  // (4-wave blocks: 2 waves per SIMD, <= 256 VGPRs, two blocks per CU)
   constexpr int NS = NSK;  // (shadows the file-wide default inside this kernel)
@@ -217,7 +233,11 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
   // Why 512 rows: every block streams all of W's planes through LDS per K-step (32 KiB), once per 256 rows before;
   // now once per 512 (a third less LDS-DMA per row), one block per CU in one round instead of two.
   constexpr bool HALVES = HEADC > 0 && WMT == 4;
-  auto tile_row = [](int i) { return HALVES ? 32 * (i & 1) + 256 * (i >> 1) : 32 * i; };
+  constexpr int RT = 2 * WMT, CT = 4;  // 16-row and 16-column MFMA tiles of the wave tile
+  auto tile_row = [](int t) {  // first row (within the wave's rows) of 16-row tile t
+    const int i = t >> 1;
+    return (HALVES ? 32 * (i & 1) + 256 * (i >> 1) : 32 * i) + 16 * (t & 1);
+  };
   static_assert(HEADC == 0 || G::SMEM <= hblk::LDS_BYTES, "the prefetch scratch KiB sits past the ring and the head");
   constexpr int STAGE = G::STAGE, GLDS_PER_STAGE = G::GLDS_PER_STAGE;
   constexpr int SMEM_BYTES = HEADC ? std::max(G::SMEM, hblk::LDS_BYTES) + 1024 : G::SMEM;  // (+ the prefetch scratch)
@@ -229,67 +249,67 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
   // static priority for the second-dispatched half (waves w and w + WAVES / 2 share a SIMD): the guide's
   // MI355X_MICROARCH "Two waves per SIMD" item 4 (knob, off by default until measured here)
   if (p.prio && wave >= G::WAVES / 2) __builtin_amdgcn_s_setprio(1);
-  const int h = lane >> 5, r32 = lane & 31;
+  const int g16 = lane >> 4, r16 = lane & 15;  // the 16x16x32 lane map: k-group / C row quad, and row or column
   U8_STAMP(0, __builtin_amdgcn_s_memrealtime);
   U8_STAMP(1, __builtin_amdgcn_s_memtime);
   // the head's W2, biases and targets (and fc1's bias): requested inside the K loop (K-step nk - 4), used after it.
   // (Requested here, at the start, they cost as much in the prologue as they saved in the epilogue: 256 blocks x 8
   // waves x 8 KB of W2 reads in one burst with the first DMA stages, stamps r5)
   hblk::Operands hops;
-  float hb1[2];
+  float hb1[CT];
 
-  f32x16 acc[WMT][2];
+  // acc[t][c][v]: row tile_row(t) + 4 g16 + v, column 16 c + r16 of the wave tile
+  f32x4 acc[RT][CT];
 #pragma unroll
-  for (int i = 0; i < WMT; ++i)
+  for (int t = 0; t < RT; ++t)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{};
+    for (int c = 0; c < CT; ++c) acc[t][c] = f32x4{};
 
-  // per-lane LDS read offsets (bytes, within a stage). k order inside a K-step, identical for both
-  // operands: lane half h, substep s, element j <-> k = (FBK / 2) h + 8 s + j, so the lane's
-  // FBK / 2 contiguous pixel bytes of a row feed all substeps of the X operand.
-  // (the swizzles use row bits below 5 only, so tiles 32 rows apart differ by a constant offset)
-  int aoff[XCH / 2], boff[NSUB];
+  // per-lane LDS read offsets (bytes, within a stage). k order inside a K-step, identical for both operands: k-group
+  // g = lane >> 4, substep s, element j <-> k = 16 g + 8 s + j, so the lane's 16 contiguous pixel bytes of a row (chunk
+  // g, one ds_read_b128 per row tile) feed both substeps of the X operand, and a weight fragment is chunk 2 g + s.
+  // (the swizzles use row bits below 4 only, so tiles 16 rows apart differ by a constant offset)
+  int aoff, boff[NSUB];
   {
-    const int row = (HALVES ? wm * 64 : wm * 32 * WMT) + r32;
-#pragma unroll
-    for (int c = 0; c < XCH / 2; ++c) aoff[c] = row * FBK + 16 * xpos(row, (XCH / 2) * h + c);
+    const int row = (HALVES ? wm * 64 : wm * 32 * WMT) + r16;
+    aoff = row * FBK + 16 * xpos(row, g16);
   }
   {
-    const int row = wn * 64 + r32;
+    const int row = wn * 64 + r16;
 #pragma unroll
-    for (int s = 0; s < NSUB; ++s) boff[s] = G::A_BYTES + row * (2 * FBK) + 16 * wpos(row, NSUB * h + s);
+    for (int s = 0; s < NSUB; ++s) boff[s] = G::A_BYTES + row * (2 * FBK) + 16 * wpos(row, NSUB * g16 + s);
   }
 
-  // NS_ = substeps to run: NSUB, or fewer in the last K-step when only lane half 0's first
-  // substeps hold k < K (the rest multiply zero-padded weights)
-  auto load_a = [&](const unsigned char* st, int s2, u32x4 (&ar)[WMT]) {  // 16 B = substeps 2 s2, 2 s2 + 1
+  auto load_a = [&](const unsigned char* st, u32x4 (&ar)[RT]) {  // 16 B per row tile = both substeps
 #pragma unroll
-    for (int i = 0; i < WMT; ++i) {
-      if constexpr (MODE == 3) ar[i] = u32x4{(unsigned)aoff[s2], 1u, 2u, 3u};
-      else ar[i] = *reinterpret_cast<const u32x4*>(st + aoff[s2] + FBK * tile_row(i));
+    for (int t = 0; t < RT; ++t) {
+      if constexpr (MODE == 3) ar[t] = u32x4{(unsigned)aoff, 1u, 2u, 3u};
+      else ar[t] = *reinterpret_cast<const u32x4*>(st + aoff + FBK * tile_row(t));
     }
   };
-  auto load_b = [&](const unsigned char* st, int s, f16x8 (&b)[2][NPL]) {
+  // one column tile's weight fragments (per column tile, not per substep: a whole substep's 8 would not fit the
+  // 16-wave kernel's 128 registers)
+  auto load_b = [&](const unsigned char* st, int s, int c, f16x8 (&b)[NPL]) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int pl = 0; pl < NPL; ++pl) {
-        if constexpr (MODE == 3) b[j][pl] = __builtin_bit_cast(f16x8, bf16x8{(short)boff[s], (short)pl, (short)j, 2, 3, 4, 5, 6});
-        else b[j][pl] = *reinterpret_cast<const f16x8*>(st + boff[s] + 64 * FBK * j + pl * B_PLANE);
-      }
-  };
-  auto compute = [&](int s, const u32x4 (&ar)[WMT], const f16x8 (&b)[2][NPL]) {
-#pragma unroll
-    for (int i = 0; i < WMT; ++i) {
-      const u32x4 v = ar[i];
-      f16x8 a;
-      if constexpr (MODE == 5) a = __builtin_bit_cast(f16x8, v);  // timing only: no widening
-      else a = (s & 1) ? widen8h(v[2], v[3]) : widen8h(v[0], v[1]);
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int pl = NPL - 1; pl >= 0; --pl) acc[i][j] = mfma(a, b[j][pl], acc[i][j]);  // lo first
+    for (int pl = 0; pl < NPL; ++pl) {
+      if constexpr (MODE == 3) b[pl] = __builtin_bit_cast(f16x8, bf16x8{(short)boff[s], (short)pl, (short)c, 2, 3, 4, 5, 6});
+      else b[pl] = *reinterpret_cast<const f16x8*>(st + boff[s] + 16 * (2 * FBK) * c + pl * B_PLANE);
     }
+  };
+  auto widen = [&](int s, const u32x4 (&ar)[RT], f16x8 (&a)[RT]) {
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      const u32x4 v = ar[t];
+      if constexpr (MODE == 5) a[t] = __builtin_bit_cast(f16x8, v);  // timing only: no widening
+      else a[t] = s ? widen8h(v[2], v[3]) : widen8h(v[0], v[1]);
+    }
+  };
+  // every accumulator's chain is the same in every variant: per K-step, substep 0 lo, hi, substep 1 lo, hi
+  auto compute = [&](int c, const f16x8 (&a)[RT], const f16x8 (&b)[NPL]) {
+#pragma unroll
+    for (int pl = NPL - 1; pl >= 0; --pl)  // lo first
+#pragma unroll
+      for (int t = 0; t < RT; ++t) acc[t][c] = mfma16(a[t], b[pl], acc[t][c]);
   };
   // DMA_AT: substep after whose MFMAs a K-step issues the next stage's DMA (-1: right after the barrier, the
   // production schedule; MODE 8 / 9, experiments: after substep 0 / 1)
@@ -298,57 +318,52 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
                 "spread DMA: the 2-stage production loop, 6 pieces per wave");
   // PIPE: the pipelined K-step (MODE 11, experiments)
   constexpr bool PIPE = MODE == 11;
+  // dma_part(q): the spread form's pieces after half-substep q (two column tiles' MFMAs), q = 0..2
   auto kstep = [&](const unsigned char* st, auto ns_c, auto&& dma, auto&& dma_part) {
     constexpr int NS_ = decltype(ns_c)::value;
     if constexpr (MODE == 1) return;
-    // (reading substep s+1's fragments ahead of substep s's MFMAs, pinned with sched_barrier,
-    // measured no faster at either geometry: 87.2 vs 87.5 us; neither did s_setprio 1 around
-    // each substep's MFMAs: 92.3-92.9 vs 91.5-93.4 us)
-    if constexpr (PIPE) {
-      // register double buffer: substep s + 1's fragment reads are issued before substep s's MFMAs (pinned
-      // with sched_barrier), so each counted lgkmcnt wait covers reads that had a whole substep of MFMAs
-      // to land; the next stage's DMA goes out while substep 0's reads are in flight
-      u32x4 ar[2][WMT];
-      f16x8 b[2][2][NPL];
-      load_a(st, 0, ar[0]);
-      load_b(st, 0, b[0]);
-      dma();
+    // (on the 32x32x16 form, reading substep s+1's fragments ahead of substep s's MFMAs, pinned with sched_barrier,
+    // measured no faster at either geometry: 87.2 vs 87.5 us; neither did s_setprio 1 around each substep's MFMAs:
+    // 92.3-92.9 vs 91.5-93.4 us)
+    u32x4 ar[RT];
+    f16x8 a[RT];
+    if constexpr (PIPE || DMAS == 2) {
+      // register double buffer: the next column tile's weight fragments are read before this tile's MFMAs (PIPE:
+      // pinned with sched_barrier, the next stage's DMA issued while the first reads are in flight; DMAS 2: the
+      // compiler's own placement, with the spread DMA)
+      f16x8 b[2][NPL];
+      load_a(st, ar);
+      load_b(st, 0, 0, b[0]);
+      if constexpr (PIPE) dma();
 #pragma unroll
-      for (int s = 0; s < NS_; ++s) {
-        if (s + 1 < NS_) {
-          if ((s + 1) % 2 == 0) load_a(st, (s + 1) >> 1, ar[((s + 1) >> 1) & 1]);
-          load_b(st, s + 1, b[(s + 1) & 1]);
+      for (int q = 0; q < CT * NS_; ++q) {
+        if (q % CT == 0) widen(q / CT, ar, a);
+        if (q + 1 < CT * NS_) load_b(st, (q + 1) / CT, (q + 1) % CT, b[(q + 1) & 1]);
+        if constexpr (PIPE) __builtin_amdgcn_sched_barrier(0);
+        compute(q % CT, a, b[q & 1]);
+        if constexpr (PIPE) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (DMAS == 2) {
+          if (q & 1) dma_part(q >> 1);
         }
-        __builtin_amdgcn_sched_barrier(0);
-        compute(s, ar[(s >> 1) & 1], b[s & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else if constexpr (DMAS == 2) {
-      // spread DMA + substep s + 1's fragment reads issued ahead of substep s's MFMAs (register double buffer, the
-      // compiler's own placement: no sched_barrier)
-      u32x4 ar[2][WMT];
-      f16x8 b[2][2][NPL];
-      load_a(st, 0, ar[0]);
-      load_b(st, 0, b[0]);
-#pragma unroll
-      for (int s = 0; s < NS_; ++s) {
-        if (s + 1 < NS_) {
-          if ((s + 1) % 2 == 0) load_a(st, (s + 1) >> 1, ar[((s + 1) >> 1) & 1]);
-          load_b(st, s + 1, b[(s + 1) & 1]);
-        }
-        compute(s, ar[(s >> 1) & 1], b[s & 1]);
-        dma_part(s);
       }
     } else {
-      u32x4 ar[WMT];
-      f16x8 b[2][NPL];
+      f16x8 b[NPL];
+      load_a(st, ar);
 #pragma unroll
       for (int s = 0; s < NS_; ++s) {
-        if (s % 2 == 0) load_a(st, s >> 1, ar);
-        load_b(st, s, b);
-        compute(s, ar, b);
+        widen(s, ar, a);
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          load_b(st, s, c, b);
+          compute(c, a, b);
+          // (the 16-wave kernel's 128 registers: left alone, the scheduler hoists a whole substep's 8 weight fragments
+          // and spills; at 4 waves per SIMD the other waves cover the reads' latency)
+          if constexpr (NWR == 8) __builtin_amdgcn_sched_barrier(0);
+          if constexpr (DMAS == 1) {
+            if (c & 1) dma_part(2 * s + (c >> 1));
+          }
+        }
         if (s == DMA_AT) dma();
-        if constexpr (DMAS == 1) dma_part(s);
       }
     }
   };
@@ -401,13 +416,14 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
         [&] {
           if (NS == 2 || t + NS - 1 < nk) issue_stage<WMT, NWR>(p, nxt, m0, n0, k1, wave, lane);
         },
-        [&](int sub) {  // DMAS == 1 (NS == 2): two of the 6 pieces after each of the first three substeps
+        [&](int sub) {  // DMAS == 1 (NS == 2): two of the 6 pieces after each of the first three half-substeps
           if (sub == 0) issue_stage<WMT, NWR, 0, 2>(p, nxt, m0, n0, k1, wave, lane);
           else if (sub == 1) issue_stage<WMT, NWR, 2, 4>(p, nxt, m0, n0, k1, wave, lane);
           else if (sub == 2) issue_stage<WMT, NWR, 4, 1 << 20>(p, nxt, m0, n0, k1, wave, lane);
         });
   }
-  {  // last K-step: only the substeps holding k < K (lane half 0 covers the first FBK / 2 k)
+  {  // last K-step: only the substeps holding k < K (substep s holds k = 16 g + 8 s + j: both, unless K ends within
+     // the K-step's first 8 k)
     sync_step(nk - 1, std::integral_constant<bool, (NS > 2)>{});
     kstep(smem + ((nk - 1) % NS) * STAGE, std::integral_constant<int, TAIL>{}, no_dma, no_dma_part);
   }
@@ -415,11 +431,11 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
   if constexpr (MODE == 10) {  // timing only: the K loop alone (keep the accumulators alive)
     float keep = 0.f;
 #pragma unroll
-    for (int i = 0; i < WMT; ++i)
+    for (int t = 0; t < RT; ++t)
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int c = 0; c < CT; ++c)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) keep += acc[i][j][r];
+        for (int v = 0; v < 4; ++v) keep += acc[t][c][v];
     if (keep == 12345.f && lane == 99) p.stamps[0] = 1;
     return;
   }
@@ -428,14 +444,14 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
     long long* stp = MODE == 7 ? p.stamps + ((size_t)blockIdx.x * G::WAVES + wave) * U8_NSTAMP : nullptr;
     if constexpr (!HALVES) {
       fused_head_epilogue<HEADC, NWR>(p, acc, smem, m0, wave, lane, wm, wn, hops, hb1, stp, (int)blockIdx.x);
-    } else {  // two 256-row head blocks: tiles 0, 1 then 2, 3 of every wave (see HALVES)
-      typedef const f32x16 Half[2][2];
+    } else {  // two 256-row head blocks: row tiles 0..3 then 4..7 of every wave (see HALVES)
+      typedef const f32x4 Half[4][4];
       fused_head_epilogue<HEADC, NWR>(p, *reinterpret_cast<Half*>(&acc[0][0]), smem, m0, wave, lane, wm, wn, hops, hb1,
                                       stp, 2 * (int)blockIdx.x);
       if (m0 + hblk::ROWS < p.M) {  // (block-uniform) the second half holds rows
         __syncthreads();  // every wave is done with the first head's LDS
         fused_head_prefetch<HEADC>(p, m0 + hblk::ROWS, wave, lane, wn, hops, hb1);
-        fused_head_epilogue<HEADC, NWR>(p, *reinterpret_cast<Half*>(&acc[2][0]), smem, m0 + hblk::ROWS, wave, lane, wm,
+        fused_head_epilogue<HEADC, NWR>(p, *reinterpret_cast<Half*>(&acc[4][0]), smem, m0 + hblk::ROWS, wave, lane, wm,
                                         wn, hops, hb1, nullptr, 2 * (int)blockIdx.x + 1);
       }
     }
@@ -447,24 +463,26 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
   // 16-byte row pieces, EPR rows of the wave tile at a time (EPR x 64 fp32 per wave; the waves'
   // pieces reuse the stage buffers, free after the barrier that ended the last K-step)
   __syncthreads();
-  constexpr int EPR = G::EPR, NI2 = EPR / 32;
+  // (row rr of a piece keeps its 64 columns rotated by 16 (rr >> 2): a C register's four row quads, 64 dwords apart,
+  // would share 16 banks; the rotation keeps every 16-byte piece whole)
+  constexpr int EPR = G::EPR, NI2 = EPR / 16;
   float* T = reinterpret_cast<float*>(smem) + wave * EPR * 64;
-  float bv[2];
+  float bv[CT];
 #pragma unroll
-  for (int j = 0; j < 2; ++j) bv[j] = p.bias ? p.bias[n0 + wn * 64 + 32 * j + r32] : 0.f;
+  for (int c = 0; c < CT; ++c) bv[c] = p.bias ? p.bias[n0 + wn * 64 + 16 * c + r16] : 0.f;
   float vmax = 0.f;
 #pragma unroll
-  for (int ip = 0; ip < WMT / NI2; ++ip) {
+  for (int ip = 0; ip < RT / NI2; ++ip) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous piece's reads are done
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int c = 0; c < CT; ++c)
 #pragma unroll
       for (int i2 = 0; i2 < NI2; ++i2)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float y = acc[NI2 * ip + i2][j][r] * p.scale + bv[j];
+        for (int v = 0; v < 4; ++v) {
+          float y = acc[NI2 * ip + i2][c][v] * p.scale + bv[c];
           if (p.relu) y = fmaxf(y, 0.f);
-          T[(32 * i2 + (r & 3) + 8 * (r >> 2) + 4 * h) * 64 + 32 * j + r32] = y;
+          T[(16 * i2 + 4 * g16 + v) * 64 + ((16 * c + r16 + 16 * (4 * i2 + g16)) & 63)] = y;
         }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's piece is in LDS (wave-private region)
     __builtin_amdgcn_wave_barrier();
@@ -472,7 +490,7 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
     for (int q = 0; q < EPR / 4; ++q) {
       const int rr = 4 * q + (lane >> 4);
       const int row = m0 + wm * 32 * WMT + EPR * ip + rr;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(T + rr * 64 + 4 * (lane & 15));
+      const f32x4 v = *reinterpret_cast<const f32x4*>(T + rr * 64 + ((4 * (lane & 15) + 16 * q) & 63));
       if constexpr (MODE == 6) {  // timing only: no global stores (keep the values alive)
         if (v[0] == 12345.f && row < 0) *reinterpret_cast<f32x4*>(p.C) = v;
       } else if (row < p.M) {
@@ -496,35 +514,62 @@ __global__ void __launch_bounds__(128 * NWR, NWR == 2 ? 2 : 1) u8_fwd_kernel(Fwd
   }
 }
 
-// ReLU-bit words of tile (i, j) = (Q >> 5, (Q >> 4) & 1), registers r = Q & 15 .. +3 (rows rw = 32 i + 8 (r >> 2) + e
-// and rw + 4 of the wave, e = 0..3): each ballot's halves go to lanes rw and rw + 4 of mw[j] (lane selects inline
-// constants). The ballots are VALU writes of SGPRs that v_writelane reads as data: the hazard recognizer does not look
-// into the asm string, so it opens with the wait states itself (without them a writelane read the previous ballot).
-template <int Q>
-__device__ __forceinline__ void mask_words(const f32x16 (&y)[2][2], int (&mw)[2]) {
-  if constexpr (Q < 64) {
-    constexpr int i = Q >> 5, j = (Q >> 4) & 1, r = Q & 15, rw = 32 * i + 8 * (r >> 2);
-    const unsigned long long b0 = __ballot(y[i][j][r] > 0.f), b1 = __ballot(y[i][j][r + 1] > 0.f);
-    const unsigned long long b2 = __ballot(y[i][j][r + 2] > 0.f), b3 = __ballot(y[i][j][r + 3] > 0.f);
-    asm("s_nop 4\n\t"
-        "v_writelane_b32 %0, %1, %9\n\tv_writelane_b32 %0, %2, %10\n\t"
-        "v_writelane_b32 %0, %3, %11\n\tv_writelane_b32 %0, %4, %12\n\t"
-        "v_writelane_b32 %0, %5, %13\n\tv_writelane_b32 %0, %6, %14\n\t"
-        "v_writelane_b32 %0, %7, %15\n\tv_writelane_b32 %0, %8, %16"
-        : "+v"(mw[j])
-        : "s"((unsigned)b0), "s"((unsigned)(b0 >> 32)), "s"((unsigned)b1), "s"((unsigned)(b1 >> 32)),
-          "s"((unsigned)b2), "s"((unsigned)(b2 >> 32)), "s"((unsigned)b3), "s"((unsigned)(b3 >> 32)),
-          "i"(rw), "i"(rw + 4), "i"(rw + 1), "i"(rw + 5), "i"(rw + 2), "i"(rw + 6), "i"(rw + 3), "i"(rw + 7));
-    mask_words<Q + 4>(y, mw);
+// ReLU-bit words of the wave's 64 rows from the 16x16 C map. The ballot of register v of tile (t, c) holds, in bits
+// 16 q .. 16 q + 15, row 16 t + 4 q + v at hidden units 16 c .. + 15, so word j (hidden 32 j .. + 31) of that row is
+// the q-th 16-bit piece of tile (t, 2 j)'s ballot under that of tile (t, 2 j + 1)'s. The words are built on the scalar
+// unit and deposited into lane (row) of mw[j] by v_writelane.
+// (two 16-bit pieces as one v2i16 of scalars: hipcc selects s_pack_ll_b32_b16 / s_pack_hh_b32_b16, one instruction
+// per word; written as shifts, masks and ORs it took three)
+typedef unsigned short mw_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pack_ll(unsigned a, unsigned b) {
+  return __builtin_bit_cast(unsigned, mw_u16x2{(unsigned short)a, (unsigned short)b});
+}
+__device__ __forceinline__ unsigned pack_hh(unsigned a, unsigned b) {
+  return __builtin_bit_cast(unsigned, mw_u16x2{(unsigned short)(a >> 16), (unsigned short)(b >> 16)});
+}
+// one row tile t per call: its 16 ballots first, then the 32 words, then the deposits - a scalar pack right behind the
+// compare that writes its operand waits for the vector unit every time (stamps: +1.2K cycles per head over the batch)
+template <int t>
+__device__ __forceinline__ void mask_words(const f32x4 (&y)[4][4], int (&mw)[2]) {
+  if constexpr (t < 4) {
+    unsigned long long bl[4][4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) bl[v][c] = __ballot(y[t][c][v] > 0.f);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      unsigned w[2][4];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const unsigned long long lo = bl[v][2 * j], hi = bl[v][2 * j + 1];
+        w[j][0] = pack_ll((unsigned)lo, (unsigned)hi);
+        w[j][1] = pack_hh((unsigned)lo, (unsigned)hi);
+        w[j][2] = pack_ll((unsigned)(lo >> 32), (unsigned)(hi >> 32));
+        w[j][3] = pack_hh((unsigned)(lo >> 32), (unsigned)(hi >> 32));
+      }
+      // (the hazard recognizer does not look into the asm string: it opens with the wait states a v_writelane needs
+      // after a VALU write of an SGPR it reads, should the compiler hand it a ballot half unchanged)
+      asm("s_nop 4\n\t"
+          "v_writelane_b32 %0, %2, %10\n\tv_writelane_b32 %0, %3, %11\n\t"
+          "v_writelane_b32 %0, %4, %12\n\tv_writelane_b32 %0, %5, %13\n\t"
+          "v_writelane_b32 %1, %6, %10\n\tv_writelane_b32 %1, %7, %11\n\t"
+          "v_writelane_b32 %1, %8, %12\n\tv_writelane_b32 %1, %9, %13"
+          : "+v"(mw[0]), "+v"(mw[1])
+          : "s"(w[0][0]), "s"(w[0][1]), "s"(w[0][2]), "s"(w[0][3]), "s"(w[1][0]), "s"(w[1][1]), "s"(w[1][2]),
+            "s"(w[1][3]), "i"(16 * t + v), "i"(16 * t + 4 + v), "i"(16 * t + 8 + v), "i"(16 * t + 12 + v));
+    }
+    mask_words<t + 1>(y, mw);
   }
 }
 
 // The classifier head on the block's h, straight from the forward's accumulators (no HBM round trip): h = relu(scale
 // acc + b1) (rows past M zero) handed to head_block.h: fp16-plane MFMA logits, softmax / NLL / dl, dW2 and the block's
 // slab row, bit-identical dl to head_xent.hip's standalone block head on the same rows. The ReLU bits leave by one
-// 8-byte store per lane: each register's ballot holds one word of two rows of the wave (lanes 0..31: row rw, 32..63:
-// row rw + 4), deposited straight into those rows' lanes by v_writelane (round 4 selected them with compares, and the
-// 64 ballot SGPR pairs spilled)
+// 8-byte store per lane: each register's ballot holds 16 bits of four rows of the wave, and a row's word (two tiles'
+// pieces) is deposited straight into that row's lane by v_writelane (mask_words; round 4 selected them with compares,
+// and the 64 ballot SGPR pairs spilled)
 template <int C>
 __device__ __forceinline__ hblk::Args fused_head_args(const FwdParams& p, int hb) {  // hb: 256-row head block index
   const U8HeadArgs& hd = p.head;
@@ -542,45 +587,46 @@ __device__ __forceinline__ hblk::Args fused_head_args(const FwdParams& p, int hb
 
 template <int C>
 __device__ __forceinline__ void fused_head_prefetch(const FwdParams& p, int m0, int wave, int lane, int wn,
-                                                    hblk::Operands& ops, float (&bv1)[2]) {
+                                                    hblk::Operands& ops, float (&bv1)[4]) {
   hblk::load_operands<C>(fused_head_args<C>(p, 0), m0, p.M, wave, lane, ops);
 #pragma unroll
-  for (int j = 0; j < 2; ++j) bv1[j] = p.bias[wn * 64 + 32 * j + (lane & 31)];
+  for (int c = 0; c < 4; ++c) bv1[c] = p.bias[wn * 64 + 16 * c + (lane & 15)];
 }
 
 template <int C, int NWR>
-__device__ __forceinline__ void fused_head_epilogue(const FwdParams& p, const f32x16 (&acc)[2][2], unsigned char* smem,
+__device__ __forceinline__ void fused_head_epilogue(const FwdParams& p, const f32x4 (&acc)[4][4], unsigned char* smem,
                                                     int m0, int wave, int lane, int wm, int wn,
-                                                    const hblk::Operands& ops, const float (&bv1)[2], long long* stamp,
+                                                    const hblk::Operands& ops, const float (&bv1)[4], long long* stamp,
                                                     int hb) {
   static_assert(NWR == 4, "head_block.h: 8 waves of 64 x 64, 256 rows");
   const U8HeadArgs& hd = p.head;
-  const int h2 = lane >> 5;
+  const int g16 = lane >> 4;
   if (stamp && lane == 0) stamp[16] = (long long)__builtin_amdgcn_s_memtime();
   const hblk::Args a = fused_head_args<C>(p, hb);
-  auto prep = [&](hblk::hb_f32x16 (&y)[2][2]) {
+  // y[t][c][v] = h[64 wm + 16 t + 4 g16 + v][64 wn + 16 c + (lane & 15)]: head_block.h's Map16
+  auto prep = [&](hblk::hb_f32x4 (&y)[4][4]) {
     // the plain epilogue's fmaxf(fma(acc, scale, b), 0), the fmas on pairs (v_pk_fma_f32: the same roundings)
     const hblk::hb_f32x2 sc2 = {p.scale, p.scale};
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const hblk::hb_f32x2 b2 = {bv1[j], bv1[j]};
+      for (int c = 0; c < 4; ++c) {
+        const hblk::hb_f32x2 b2 = {bv1[c], bv1[c]};
 #pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const hblk::hb_f32x2 v = __builtin_elementwise_fma(hblk::hb_f32x2{acc[i][j][r], acc[i][j][r + 1]}, sc2, b2);
-          y[i][j][r] = fmaxf(v[0], 0.f);
-          y[i][j][r + 1] = fmaxf(v[1], 0.f);
+        for (int v = 0; v < 4; v += 2) {
+          const hblk::hb_f32x2 x = __builtin_elementwise_fma(hblk::hb_f32x2{acc[t][c][v], acc[t][c][v + 1]}, sc2, b2);
+          y[t][c][v] = fmaxf(x[0], 0.f);
+          y[t][c][v + 1] = fmaxf(x[1], 0.f);
         }
       }
     if (m0 + hblk::ROWS > p.M) {  // (block-uniform) the last block's rows past M
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int c = 0; c < 4; ++c)
 #pragma unroll
-          for (int r = 0; r < 16; ++r)
-            if (m0 + wm * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h2 >= p.M) y[i][j][r] = 0.f;
+          for (int v = 0; v < 4; ++v)
+            if (m0 + wm * 64 + 16 * t + 4 * g16 + v >= p.M) y[t][c][v] = 0.f;
     }
     int mw[2] = {0, 0};  // lane L: mask words 2 wn + j of the wave's row L
     mask_words<0>(y, mw);
@@ -605,7 +651,7 @@ __device__ __forceinline__ void fused_head_epilogue(const FwdParams& p, const f3
     }
   };
   hblk::block_head<C>(prep, smem, a, ops, m0, p.M, wave, lane, [](int, int, bool, const float (&)[4]) {}, stamp,
-                      post_b1);
+                      post_b1, hblk::Map16{});
   if (pf) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the scratch DMA lands before the LDS is released)
 }
 
@@ -1653,8 +1699,6 @@ static void launch_slab_head_reduce(const float* slab, int64_t stride, int split
 
 }  // namespace
 
-// substeps of the last K-step that hold k < K (lane half 0 covers its first FBK / 2 k; the rest
-// multiply zero-padded weights)
 static int wgrad_xcd() {
   return knob(KNOB_U8_WGRAD_XCD);
 }
@@ -1676,12 +1720,11 @@ static unsigned* wgrad_pair_words(hipStream_t stream) {
   return words[dev];
 }
 
+// MFMA substeps of the last K-step, which holds v valid k: substep s covers k = 16 g + 8 s + j (g = 0..3, j = 0..7),
+// so substep 1 is needed as soon as v > 8 - always, for the K % 16 == 0 that u8_fwd_supported admits
 static int tail_substeps(int K) {
   const int v = K - ((K + FBK - 1) / FBK - 1) * FBK;
-  if (v > FBK / 2 - 8) return NSUB;
-  if (NSUB == 4 && v > 16) return 3;
-  if (NSUB == 4 && v > 8) return 2;
-  return 1;
+  return v > 8 ? NSUB : 1;
 }
 
 int u8_fwd_kpad(int K) { return (K + FBK - 1) / FBK * FBK; }  // zero-padded W planes
@@ -1888,8 +1931,6 @@ void u8_fwd(const unsigned char* X, int M, int K, int ldx, const unsigned short*
   do {                                           \
     switch (tail) {                              \
       case 1: FWD_LAUNCH(0, W, 1, R); break;     \
-      case 2: FWD_LAUNCH(0, W, 2, R); break;     \
-      case 3: FWD_LAUNCH(0, W, 3, R); break;     \
       default: FWD_LAUNCH(0, W, NSUB, R);        \
     }                                            \
   } while (0)
@@ -2025,8 +2066,6 @@ void u8_fwd_head(const unsigned char* X, int M, int K, int ldx, const unsigned s
     p.stamps = g_u8_stamps;
     switch (tail) {
       case 1: hipLaunchKernelGGL((u8_fwd_kernel<7, 2, 1, 4, 10>), grid, dim3(512), 0, stream, p); break;
-      case 2: hipLaunchKernelGGL((u8_fwd_kernel<7, 2, 2, 4, 10>), grid, dim3(512), 0, stream, p); break;
-      case 3: hipLaunchKernelGGL((u8_fwd_kernel<7, 2, 3, 4, 10>), grid, dim3(512), 0, stream, p); break;
       default: hipLaunchKernelGGL((u8_fwd_kernel<7, 2, NSUB, 4, 10>), grid, dim3(512), 0, stream, p);
     }
     return;
@@ -2046,16 +2085,12 @@ void u8_fwd_head(const unsigned char* X, int M, int K, int ldx, const unsigned s
   do {                                    \
     switch (tail) {                       \
       case 1: FH_LAUNCH(1, CC); break;    \
-      case 2: FH_LAUNCH(2, CC); break;    \
-      case 3: FH_LAUNCH(3, CC); break;    \
       default: FH_LAUNCH(NSUB, CC);       \
     }                                     \
   } while (0)
   if (head.C == 10 && knob(KNOB_U8_FH_STAGES) == 3) {  // 3-stage ring (the 784-128-10 MLP)
     switch (tail) {
       case 1: FH_LAUNCH3(1); break;
-      case 2: FH_LAUNCH3(2); break;
-      case 3: FH_LAUNCH3(3); break;
       default: FH_LAUNCH3(NSUB);
     }
     return;

@@ -23,6 +23,9 @@ import json, statistics
 rows = [json.loads(l) for l in open("gpurun_out/ab.jsonl")]
 for b in ("base", "new"):
     ms = [r["ms_per_step"] for r in rows if r["build"] == b]
-    med = [r["step_ms_events"]["median"] for r in rows if r["build"] == b]
-    print(b, "ms_per_step", ms, "median step", round(statistics.median(med), 4))
+    # (bench.py's default events, "ends", time the first step and the mean of the rest; "all" gives a median)
+    ev = [r.get("step_ms_events") or {} for r in rows if r["build"] == b]
+    med = [e.get("median", e.get("rest_mean")) for e in ev]
+    med = [m for m in med if m is not None]
+    print(b, "ms_per_step", ms, "median step", round(statistics.median(med), 4) if med else None)
 PY
