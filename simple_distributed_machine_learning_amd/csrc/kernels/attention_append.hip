@@ -7,15 +7,14 @@
 // A dead query (t >= nq[b], or a row lens[b] + t at or past the host's bound n_keys) writes no cache row and returns
 // exact zeros. lens is not changed.
 //
-// Bit contract: query (b, t) gets the bits attention_decode.hip gives that token with lens[b] + t keys cached. The
-// arithmetic below is that kernel's, per query: the same kAttnDecodeChunk-key chunks, one wave each, the same lane ->
-// (row group, channel piece) mapping and fma chains, the same DPP reductions, the same combine in chunk order
-// (tests/test_attention_append_gpu.py compares the raw bits). The gain over T calls: a chunk's K and V rows go to
-// VGPRs once and serve all T queries.
+// Bit contract: query (b, t) gets the bits attention_decode.hip gives that token with lens[b] + t keys cached: both
+// run attn_chunk.h's chunk_query per (query, chunk) with the same chunks and lane mapping, and its combine_chunks in
+// chunk order (tests/test_attention_append_gpu.py compares the raw bits). The gain over T calls: a chunk's K and V rows
+// go to VGPRs once and serve all T queries.
 //
 // Keys: index j < lens[b] comes from the cache; j = lens[b] + r, r < nq[b], from row r of qkv; nothing is read from
-// cache rows >= lens[b] (they may hold anything). Keys past a query's own index are selected away as in
-// attention_decode.hip (their loads are redirected to a live row of qkv, so the unused operands are finite). A chunk
+// cache rows >= lens[b] (they may hold anything). Keys past a query's own index are selected away by chunk_query
+// (their loads are redirected to a live row of qkv, so the unused operands are finite). A chunk
 // is live for query t iff c * CH <= lens[b] + t. The chunk that contains index lens[b] + r owns that row's cache
 // write, and takes the key from qkv, so no wave reads a row that another wave writes.
 //
@@ -25,30 +24,12 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
-#include "wave_ops.h"
+#include "attn_chunk.h"
 
 namespace sdml {
 namespace {
 
-typedef unsigned short u16;
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int CH = kAttnDecodeChunk;  // keys per wave
-constexpr int RPL = CH / 8;           // rows per lane (8 lanes hold one row)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr int ROR8 = 0x128;  // DPP row_ror:8: lane i <- lane i ^ 8 inside a row of 16
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
-__device__ __forceinline__ u16 f2bf(float f) {
-  __hip_bfloat16 h = __float2bfloat16(f);
-  return *reinterpret_cast<u16*>(&h);
-}
-
-// sum / max over the 8 row groups of a wave (lane bits 3..5), as in attention_decode.hip
-__device__ __forceinline__ float sum_groups(float x) { return wv::sum_rows(x + wv::dpp<ROR8>(x)); }
-__device__ __forceinline__ float max_groups(float x) { return wv::max_rows(fmaxf(x, wv::dpp<ROR8>(x))); }
+using namespace attn_chunk;
 
 // live queries of sample b given its length: t < nq[b], and row len + t inside the host's bound (so inside the
 // cache and the workspace's chunks). 0 for a length outside the cache.
@@ -94,61 +75,17 @@ __global__ void __launch_bounds__(64) attn_append_chunk_kernel(AttnAppendArgs p)
     }
   }
 
-  const float sl2 = p.scale * kLog2e;
   for (int t = 0; t < n; ++t) {  // (wave-uniform)
     const int lt = len + t;      // the query's own key index: keys 0 .. lt
     if (c * CH > lt) continue;
-    const u16x8 qv = *reinterpret_cast<const u16x8*>(qrow0 + (int64_t)t * p.ldq);
-    float q[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) q[e] = bf2f(qv[e]);
-
-    float s[RPL];
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-      const int j = c * CH + 8 * i + rg;
-      float a = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) a = fmaf(q[e], bf2f(kv[i][e]), a);
-      a += wv::dpp<wv::XOR1>(a);
-      a += wv::dpp<wv::XOR2>(a);
-      a += wv::dpp<wv::HALF_MIRROR>(a);  // the row's 8 lanes hold the same sum
-      s[i] = j <= lt ? a * sl2 : -INFINITY;
-      m = fmaxf(m, s[i]);
-    }
-    m = max_groups(m);  // finite: key c * CH <= lt is in this chunk
-
-    float l = 0.f, o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = 0.f;
-#pragma unroll
-    for (int i = 0; i < RPL; ++i) {
-      const int j = c * CH + 8 * i + rg;
-      const float pr = j <= lt ? __builtin_amdgcn_exp2f(s[i] - m) : 0.f;
-      l += pr;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = fmaf(pr, bf2f(vv[i][e]), o[e]);
-    }
-    l = sum_groups(l);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = sum_groups(o[e]);
-
-    const int64_t slot = (((int64_t)b * p.T + t) * p.H + h) * p.max_chunks + c;
-    if (lane < 8) {
-      f32x4* dst = reinterpret_cast<f32x4*>(p.ws_o + slot * 64 + 8 * pc);
-      dst[0] = f32x4{o[0], o[1], o[2], o[3]};
-      dst[1] = f32x4{o[4], o[5], o[6], o[7]};
-    }
-    if (lane == 0) {
-      p.ws_ml[slot * 2] = m;
-      p.ws_ml[slot * 2 + 1] = l;
-    }
+    float m, l, o[8];
+    chunk_query(kv, vv, qrow0 + (int64_t)t * p.ldq, c, lt, p.scale, lane, m, l, o, NoRowHook{});
+    store_slot(p.ws_ml, p.ws_o, (((int64_t)b * p.T + t) * p.H + h) * p.max_chunks + c, lane, m, l, o);
   }
 }
 
-// grid (H, T, B), one wave per block, lane = channel: the chunks of one (b, t, h) in chunk order (attention_decode.hip
-// combine_chunks); a dead query's row is zeros
+// grid (H, T, B), one wave per block, lane = channel: the chunks of one (b, t, h) in chunk order; a dead
+// query's row is zeros
 __global__ void __launch_bounds__(64) attn_append_combine_kernel(AttnAppendArgs p) {
   const int h = blockIdx.x, t = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
   const int len = p.lens[b];
@@ -158,16 +95,7 @@ __global__ void __launch_bounds__(64) attn_append_combine_kernel(AttnAppendArgs 
     return;
   }
   const int nc = (len + t) / CH + 1;  // <= max_chunks: len + t < n_keys
-  const int64_t slot = (((int64_t)b * p.T + t) * p.H + h) * p.max_chunks;
-  float M = -INFINITY;
-  for (int c = 0; c < nc; ++c) M = fmaxf(M, p.ws_ml[(slot + c) * 2]);
-  float L = 0.f, O = 0.f;
-  for (int c = 0; c < nc; ++c) {
-    const float w = __builtin_amdgcn_exp2f(p.ws_ml[(slot + c) * 2] - M);
-    L = fmaf(p.ws_ml[(slot + c) * 2 + 1], w, L);
-    O = fmaf(p.ws_o[(slot + c) * 64 + lane], w, O);
-  }
-  *dst = f2bf(O / L);
+  *dst = combine_chunks(p.ws_ml, p.ws_o, (((int64_t)b * p.T + t) * p.H + h) * p.max_chunks, nc, lane);
 }
 
 }  // namespace

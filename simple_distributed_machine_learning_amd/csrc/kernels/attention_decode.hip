@@ -23,58 +23,28 @@
 // multiplied by zero. The chunk that contains index lens[b] owns the cache write, and takes that key from qkv, so no
 // wave reads a row that another wave writes.
 //
-// Rounding: scores, exp2, sums and the combine are fp32; the output is rounded to bf16 once.
+// The arithmetic of a chunk, the slot layout and the chunk-order combine are attn_chunk.h's, shared with
+// attention_append.hip, whose queries get this kernel's bits by calling the same lines.
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
+#include "attn_chunk.h"
 #include "handoff.h"
-#include "kernels.h"
-#include "wave_ops.h"
 
 namespace sdml {
 namespace {
 
-typedef unsigned short u16;
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int CH = kAttnDecodeChunk;  // keys per wave
-constexpr int RPL = CH / 8;           // rows per lane (8 lanes hold one row)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr int ROR8 = 0x128;  // DPP row_ror:8: lane i <- lane i ^ 8 inside a row of 16
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
-__device__ __forceinline__ u16 f2bf(float f) {
-  __hip_bfloat16 h = __float2bfloat16(f);
-  return *reinterpret_cast<u16*>(&h);
-}
-
-// sum / max over the 8 row groups of a wave (lane bits 3..5); lanes that differ only in those bits hold the addends
-__device__ __forceinline__ float sum_groups(float x) { return wv::sum_rows(x + wv::dpp<ROR8>(x)); }
-__device__ __forceinline__ float max_groups(float x) { return wv::max_rows(fmaxf(x, wv::dpp<ROR8>(x))); }
-
-// lane = channel: the nc chunks of one (b, h) in chunk order
-__device__ __forceinline__ void combine_chunks(const AttnDecodeArgs& p, int b, int h, int nc, int lane) {
-  const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks;
-  float M = -INFINITY;
-  for (int c = 0; c < nc; ++c) M = fmaxf(M, p.ws_ml[(slot + c) * 2]);
-  float L = 0.f, O = 0.f;
-  for (int c = 0; c < nc; ++c) {
-    const float w = __builtin_amdgcn_exp2f(p.ws_ml[(slot + c) * 2] - M);
-    L = fmaf(p.ws_ml[(slot + c) * 2 + 1], w, L);
-    O = fmaf(p.ws_o[(slot + c) * 64 + lane], w, O);
-  }
-  static_cast<u16*>(p.out)[(int64_t)b * p.H * 64 + h * 64 + lane] = f2bf(O / L);
-}
+using namespace attn_chunk;
 
 __device__ __forceinline__ float lane_value(float x, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
 }
 
-// combine_chunks for slots that other workgroups wrote in this launch, behind the caller's acquire: every load of
-// them bypasses the L1 (handoff.h), and since such a load is a round trip to the L2 or beyond, none depends on another. Lane c fetches
-// chunk c's (m, l) and computes its weight, the partial outputs are fetched eight chunks at a time; each lane then
-// runs combine_chunks' fmaf chain in chunk order on the same operands (the max is exact in any order): the same bits.
+// attn_chunk.h's combine_chunks for slots that other workgroups wrote in this launch, behind the caller's acquire:
+// every load of them bypasses the L1 (handoff.h), and since such a load is a round trip to the L2 or beyond, none
+// depends on another. Lane c fetches chunk c's (m, l) and computes its weight, the partial outputs are fetched eight
+// chunks at a time; each lane then runs combine_chunks' fmaf chain in chunk order on the same operands (the max is
+// exact in any order): the same bits.
 __device__ __forceinline__ void combine_handed_off(const AttnDecodeArgs& p, int b, int h, int nc, int lane) {
   const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks;
   const float* ml = p.ws_ml + slot * 2;
@@ -139,46 +109,13 @@ __global__ void __launch_bounds__(64) attn_decode_chunk_kernel(AttnDecodeArgs p)
     const bool cached = j < len;
     vv[i] = *reinterpret_cast<const u16x8*>(cached ? vc + (int64_t)j * p.ss : vnew);
   }
-  const u16x8 qv = *reinterpret_cast<const u16x8*>(qrow);
-  float q[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) q[e] = bf2f(qv[e]);
-
-  const float sl2 = p.scale * kLog2e;
-  float s[RPL];
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < RPL; ++i) {
-    const int j = c * CH + 8 * i + rg;
+  float m, l, o[8];
+  chunk_query(kv, vv, qrow, c, len, p.scale, lane, m, l, o, [&](int i, int j) {
     if (j == len) {  // the new token's row: bit for bit from qkv
       *reinterpret_cast<u16x8*>(kc + (int64_t)j * p.ss) = kv[i];
       *reinterpret_cast<u16x8*>(vc + (int64_t)j * p.ss) = vv[i];
     }
-    float a = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) a = fmaf(q[e], bf2f(kv[i][e]), a);
-    a += wv::dpp<wv::XOR1>(a);
-    a += wv::dpp<wv::XOR2>(a);
-    a += wv::dpp<wv::HALF_MIRROR>(a);  // the row's 8 lanes hold the same sum
-    s[i] = j <= len ? a * sl2 : -INFINITY;
-    m = fmaxf(m, s[i]);
-  }
-  m = max_groups(m);  // finite: key c * CH <= len is in this chunk
-
-  float l = 0.f, o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = 0.f;
-#pragma unroll
-  for (int i = 0; i < RPL; ++i) {
-    const int j = c * CH + 8 * i + rg;
-    const float pr = j <= len ? __builtin_amdgcn_exp2f(s[i] - m) : 0.f;
-    l += pr;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = fmaf(pr, bf2f(vv[i][e]), o[e]);
-  }
-  l = sum_groups(l);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = sum_groups(o[e]);
+  });
 
   const int64_t slot = ((int64_t)b * p.H + h) * p.max_chunks + c;
   if constexpr (TK) {
@@ -196,15 +133,7 @@ __global__ void __launch_bounds__(64) attn_decode_chunk_kernel(AttnDecodeArgs p)
     combine_handed_off(p, b, h, len / CH + 1, lane);
     if (lane == 0) handoff::reset_ticket(counter);
   } else {
-    if (lane < 8) {
-      f32x4* dst = reinterpret_cast<f32x4*>(p.ws_o + slot * 64 + 8 * pc);
-      dst[0] = f32x4{o[0], o[1], o[2], o[3]};
-      dst[1] = f32x4{o[4], o[5], o[6], o[7]};
-    }
-    if (lane == 0) {
-      p.ws_ml[slot * 2] = m;
-      p.ws_ml[slot * 2 + 1] = l;
-    }
+    store_slot(p.ws_ml, p.ws_o, slot, lane, m, l, o);
   }
 }
 
@@ -215,7 +144,8 @@ __global__ void __launch_bounds__(64) attn_decode_combine_kernel(AttnDecodeArgs 
   if (len < 0 || len >= p.Smax) return;
   const int nc = len / CH + 1;  // <= max_chunks: the host checked lens[b] + 1 <= n_keys
   if (nc > p.max_chunks) return;
-  combine_chunks(p, b, h, nc, lane);
+  static_cast<u16*>(p.out)[(int64_t)b * p.H * 64 + h * 64 + lane] =
+      combine_chunks(p.ws_ml, p.ws_o, ((int64_t)b * p.H + h) * p.max_chunks, nc, lane);
 }
 
 }  // namespace

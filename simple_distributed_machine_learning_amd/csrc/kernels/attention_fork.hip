@@ -13,7 +13,10 @@
 // rows followed by the row's suffix rows, with lens[r] keys cached. The arithmetic below is that kernel's, per query:
 // the same kAttnDecodeChunk-key chunks at the absolute key index, one wave each, the same lane -> (row group, channel
 // piece) mapping and fma chains, the same DPP reductions, one (m, l, o[64]) slot per (r, h, chunk), the same combine
-// in chunk order in a second launch (tests/test_attention_fork_gpu.py compares the raw bits).
+// in chunk order in a second launch (tests/test_attention_fork_gpu.py compares the raw bits). That arithmetic is
+// defined in attn_chunk.h, which attention_decode.hip and attention_append.hip call; this file keeps its own copy of
+// chunk_query and the combine (on the header its chunk kernel was slower, profiles/decode_chunk_ab.jsonl), so a change
+// to attn_chunk.h must be repeated here.
 //
 // The gain: a chunk c with (c + 1) * CH <= plens[g] lies wholly in the prompt and is the same for the n siblings. The
 // block of sibling 0 loads its K and V rows to VGPRs once and runs the n queries against them in a wave-uniform loop,

@@ -2101,6 +2101,33 @@ static int* decode_tickets(const char* who, const c10::optional<torch::Tensor>& 
   return tickets->data_ptr<int>();
 }
 
+// a k / v pair [rows, keys, H, 64] of the generation attentions: bf16 on `like`'s device, one layout for both,
+// contiguous channels, strides that are multiples of 8, 16-byte aligned. `layout` / `align`: the binding's wording of
+// those two refusals, kept as each binding had it (attention_append and attention_extend report a misaligned cache
+// with their "qkv rows must be 16-byte aligned ..." text, as they always did).
+static void check_kv_pair(const char* who, const torch::Tensor& k, const torch::Tensor& v, const torch::Tensor& like,
+                          const char* layout, const char* align) {
+  TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.scalar_type() == torch::kBFloat16 &&
+                  v.scalar_type() == torch::kBFloat16 && k.dim() == 4 && k.sizes() == v.sizes() &&
+                  k.strides() == v.strides(),
+              who, ": ", layout);
+  TORCH_CHECK(k.size(3) == 64 && k.stride(3) == 1, who, ": head width 64, contiguous channels");
+  for (int d = 0; d < 3; ++d)
+    TORCH_CHECK(k.stride(d) % 8 == 0 && k.stride(d) >= 0, who, ": cache strides must be multiples of 8");
+  TORCH_CHECK(k.device() == like.device() && v.device() == like.device(), who, ": all tensors on one device");
+  TORCH_CHECK(aligned16(k) && aligned16(v), who, ": ", align);
+}
+static const char* const kOneCachePair = "k_cache / v_cache must be bf16 device tensors [B, Smax, H, 64] of one layout";
+
+// an int32 [n] vector on `like`'s device (lens, nq, plens); `dim` is n's name in the refusal
+static int* device_i32(const char* who, const char* name, const char* dim, const torch::Tensor& t, int64_t n,
+                       const torch::Tensor& like) {
+  TORCH_CHECK(t.device() == like.device(), who, ": all tensors on one device");
+  TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.is_contiguous() && t.dim() == 1 && t.numel() == n, who, ": ", name,
+              " must be int32 [", dim, "] on the device");
+  return t.data_ptr<int>();
+}
+
 // qkv [B, 3C] (the new token's fused projection), k_cache / v_cache [B, Smax, H, 64] views (any strides that are
 // multiples of 8 with contiguous channels, the same for both), lens int32 [B]: keys already cached. n_keys: the
 // host's bound lens[b] + 1 <= n_keys (it advances the lengths itself, so it knows them without reading the device).
@@ -2110,32 +2137,21 @@ torch::Tensor attention_decode(torch::Tensor qkv, torch::Tensor k_cache, torch::
                                double scale, int64_t n_keys, c10::optional<torch::Tensor> tickets) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1,
               "attention_decode: qkv must be a [B, 3C] bf16 device tensor with unit column stride");
-  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.scalar_type() == torch::kBFloat16 &&
-                  v_cache.scalar_type() == torch::kBFloat16 && k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() &&
-                  k_cache.strides() == v_cache.strides(),
-              "attention_decode: k_cache / v_cache must be bf16 device tensors [B, Smax, H, 64] of one layout");
+  check_kv_pair("attention_decode", k_cache, v_cache, qkv, kOneCachePair, "16-byte aligned rows required");
   const int64_t B = qkv.size(0), Smax = k_cache.size(1), H = k_cache.size(2), C = H * 64;
-  TORCH_CHECK(k_cache.size(3) == 64 && k_cache.stride(3) == 1, "attention_decode: head width 64, contiguous channels");
   TORCH_CHECK(k_cache.size(0) == B && qkv.size(1) == 3 * C, "attention_decode: qkv ", qkv.sizes(), " does not match a ",
               k_cache.sizes(), " cache");
-  TORCH_CHECK(k_cache.device() == qkv.device() && v_cache.device() == qkv.device() && lens.device() == qkv.device(),
-              "attention_decode: all tensors on one device");
-  for (int d = 0; d < 3; ++d)
-    TORCH_CHECK(k_cache.stride(d) % 8 == 0 && k_cache.stride(d) >= 0, "attention_decode: cache strides must be multiples of 8");
-  TORCH_CHECK(qkv.stride(0) % 8 == 0 && aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache),
-              "attention_decode: 16-byte aligned rows required");
-  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() && lens.numel() == B,
-              "attention_decode: lens must be int32 [B] on the device");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && aligned16(qkv), "attention_decode: 16-byte aligned rows required");
+  sdml::AttnDecodeArgs a;
+  a.lens = device_i32("attention_decode", "lens", "B", lens, B, qkv);
   TORCH_CHECK(n_keys >= 1 && n_keys <= Smax, "attention_decode: the cache is full: ", n_keys, " keys with the new one, ",
               Smax, " rows (lens[b] + 1 <= n_keys <= Smax)");
   TORCH_CHECK(B >= 1 && B <= 65535 && H <= 65535, "attention_decode: batch / heads out of the grid's range");
-  sdml::AttnDecodeArgs a;
   a.tickets = decode_tickets("attention_decode", tickets, qkv, B * H, "one per sample and head");
   a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
   auto out = torch::empty({B, C}, qkv.options());
   auto ws = torch::empty({B * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
   a.qkv = qkv.data_ptr(), a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr(), a.out = out.data_ptr();
-  a.lens = lens.data_ptr<int>();
   a.ws_o = ws.data_ptr<float>();
   a.ws_ml = a.ws_o + B * H * a.max_chunks * 64;
   a.B = (int)B, a.H = (int)H, a.Smax = (int)Smax;
@@ -2155,35 +2171,24 @@ torch::Tensor attention_append(torch::Tensor qkv, torch::Tensor k_cache, torch::
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(T >= 1 && T <= sdml::kAttnAppendMaxT, "attention_append: T = ", T, " new tokens per sample, 1..",
               sdml::kAttnAppendMaxT, " are supported");
-  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.scalar_type() == torch::kBFloat16 &&
-                  v_cache.scalar_type() == torch::kBFloat16 && k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() &&
-                  k_cache.strides() == v_cache.strides(),
-              "attention_append: k_cache / v_cache must be bf16 device tensors [B, Smax, H, 64] of one layout");
+  check_kv_pair("attention_append", k_cache, v_cache, qkv, kOneCachePair,
+                "qkv rows must be 16-byte aligned with one stride over [B, T]");
   const int64_t Smax = k_cache.size(1), H = k_cache.size(2), C = H * 64;
-  TORCH_CHECK(k_cache.size(3) == 64 && k_cache.stride(3) == 1, "attention_append: head width 64, contiguous channels");
   TORCH_CHECK(k_cache.size(0) == B && qkv.size(2) == 3 * C, "attention_append: qkv ", qkv.sizes(), " does not match a ",
               k_cache.sizes(), " cache");
-  TORCH_CHECK(k_cache.device() == qkv.device() && v_cache.device() == qkv.device() && lens.device() == qkv.device() &&
-                  nq.device() == qkv.device(),
-              "attention_append: all tensors on one device");
-  for (int d = 0; d < 3; ++d)
-    TORCH_CHECK(k_cache.stride(d) % 8 == 0 && k_cache.stride(d) >= 0, "attention_append: cache strides must be multiples of 8");
   TORCH_CHECK(qkv.stride(1) % 8 == 0 && qkv.stride(1) >= 3 * C && (B == 1 || qkv.stride(0) == T * qkv.stride(1)) &&
-                  aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache),
+                  aligned16(qkv),
               "attention_append: qkv rows must be 16-byte aligned with one stride over [B, T]");
-  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() && lens.dim() == 1 && lens.numel() == B,
-              "attention_append: lens must be int32 [B] on the device");
-  TORCH_CHECK(nq.scalar_type() == torch::kInt32 && nq.is_contiguous() && nq.dim() == 1 && nq.numel() == B,
-              "attention_append: nq must be int32 [B] on the device");
+  sdml::AttnAppendArgs a;
+  a.lens = device_i32("attention_append", "lens", "B", lens, B, qkv);
+  a.nq = device_i32("attention_append", "nq", "B", nq, B, qkv);
   TORCH_CHECK(n_keys >= 1 && n_keys <= Smax, "attention_append: n_keys = ", n_keys, " outside 1..", Smax,
               " (the cache's rows)");
   TORCH_CHECK(B >= 1 && B <= 65535 && H <= 65535, "attention_append: batch / heads out of the grid's range");
-  sdml::AttnAppendArgs a;
   a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
   auto out = torch::empty({B, T, C}, qkv.options());
   auto ws = torch::empty({B * T * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
   a.qkv = qkv.data_ptr(), a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr(), a.out = out.data_ptr();
-  a.lens = lens.data_ptr<int>(), a.nq = nq.data_ptr<int>();
   a.ws_o = ws.data_ptr<float>();
   a.ws_ml = a.ws_o + B * T * H * a.max_chunks * 64;
   a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Smax = (int)Smax, a.n_keys = (int)n_keys;
@@ -2202,35 +2207,24 @@ torch::Tensor attention_extend(torch::Tensor qkv, torch::Tensor k_cache, torch::
               "attention_extend: qkv must be a [B, T, 3C] bf16 device tensor with unit column stride");
   const int64_t B = qkv.size(0), T = qkv.size(1);
   TORCH_CHECK(T >= 1, "attention_extend: T = ", T, " new positions per sample, at least 1");
-  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.scalar_type() == torch::kBFloat16 &&
-                  v_cache.scalar_type() == torch::kBFloat16 && k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() &&
-                  k_cache.strides() == v_cache.strides(),
-              "attention_extend: k_cache / v_cache must be bf16 device tensors [B, Smax, H, 64] of one layout");
+  check_kv_pair("attention_extend", k_cache, v_cache, qkv, kOneCachePair,
+                "qkv rows must be 16-byte aligned with one stride over [B, T]");
   const int64_t Smax = k_cache.size(1), H = k_cache.size(2), C = H * 64;
-  TORCH_CHECK(k_cache.size(3) == 64 && k_cache.stride(3) == 1, "attention_extend: head width 64, contiguous channels");
   TORCH_CHECK(k_cache.size(0) == B && qkv.size(2) == 3 * C, "attention_extend: qkv ", qkv.sizes(), " does not match a ",
               k_cache.sizes(), " cache");
-  TORCH_CHECK(k_cache.device() == qkv.device() && v_cache.device() == qkv.device() && lens.device() == qkv.device() &&
-                  nq.device() == qkv.device(),
-              "attention_extend: all tensors on one device");
-  for (int d = 0; d < 3; ++d)
-    TORCH_CHECK(k_cache.stride(d) % 8 == 0 && k_cache.stride(d) >= 0, "attention_extend: cache strides must be multiples of 8");
   TORCH_CHECK(qkv.stride(1) % 8 == 0 && qkv.stride(1) >= 3 * C && (B == 1 || qkv.stride(0) == T * qkv.stride(1)) &&
-                  aligned16(qkv) && aligned16(k_cache) && aligned16(v_cache),
+                  aligned16(qkv),
               "attention_extend: qkv rows must be 16-byte aligned with one stride over [B, T]");
-  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() && lens.dim() == 1 && lens.numel() == B,
-              "attention_extend: lens must be int32 [B] on the device");
-  TORCH_CHECK(nq.scalar_type() == torch::kInt32 && nq.is_contiguous() && nq.dim() == 1 && nq.numel() == B,
-              "attention_extend: nq must be int32 [B] on the device");
+  sdml::AttnExtendArgs a;
+  a.lens = device_i32("attention_extend", "lens", "B", lens, B, qkv);
+  a.nq = device_i32("attention_extend", "nq", "B", nq, B, qkv);
   TORCH_CHECK(n_keys >= 1 && n_keys <= Smax, "attention_extend: n_keys = ", n_keys, " outside 1..", Smax,
               " (the cache's rows)");
   const int64_t nqb = (T + 127) / 128;
   TORCH_CHECK(B >= 1 && B <= 65535 && H >= 1 && nqb * H * B < (1LL << 31) && B * T < (1LL << 31),
               "attention_extend: batch / heads / positions out of the grid's range");
-  sdml::AttnExtendArgs a;
   auto out = torch::empty({B, T, C}, qkv.options());
   a.qkv = qkv.data_ptr(), a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr(), a.out = out.data_ptr();
-  a.lens = lens.data_ptr<int>(), a.nq = nq.data_ptr<int>();
   a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Smax = (int)Smax, a.n_keys = (int)n_keys;
   a.ldq = qkv.stride(1), a.sb = k_cache.stride(0), a.ss = k_cache.stride(1), a.sh = k_cache.stride(2);
   a.scale = (float)scale;
@@ -2251,41 +2245,27 @@ torch::Tensor attention_fork(torch::Tensor qkv, torch::Tensor kp, torch::Tensor 
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1,
               "attention_fork: qkv must be a [R, 3C] bf16 device tensor with unit column stride");
   const int64_t R = qkv.size(0);
-  for (const auto* pr : {&kp, &ks}) {
-    const torch::Tensor &k = *pr, &v = pr == &kp ? vp : vs;
-    TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.scalar_type() == torch::kBFloat16 &&
-                    v.scalar_type() == torch::kBFloat16 && k.dim() == 4 && k.sizes() == v.sizes() &&
-                    k.strides() == v.strides(),
-                "attention_fork: kp / vp and ks / vs must be bf16 device tensors [rows, keys, H, 64], each pair of one "
-                "layout");
-    TORCH_CHECK(k.size(3) == 64 && k.stride(3) == 1, "attention_fork: head width 64, contiguous channels");
-    for (int d = 0; d < 3; ++d)
-      TORCH_CHECK(k.stride(d) % 8 == 0 && k.stride(d) >= 0, "attention_fork: cache strides must be multiples of 8");
-    TORCH_CHECK(k.device() == qkv.device() && v.device() == qkv.device(), "attention_fork: all tensors on one device");
-    TORCH_CHECK(aligned16(k) && aligned16(v), "attention_fork: 16-byte aligned rows required");
-  }
+  for (const auto* pr : {&kp, &ks})
+    check_kv_pair("attention_fork", *pr, pr == &kp ? vp : vs, qkv,
+                  "kp / vp and ks / vs must be bf16 device tensors [rows, keys, H, 64], each pair of one layout",
+                  "16-byte aligned rows required");
   const int64_t G = kp.size(0), Pmax = kp.size(1), H = kp.size(2), Nmax = ks.size(1), C = H * 64;
   TORCH_CHECK(G >= 1 && R == G * n && ks.size(0) == R && ks.size(2) == H && qkv.size(1) == 3 * C, "attention_fork: qkv ",
               qkv.sizes(), " and a suffix cache ", ks.sizes(), " do not match ", n, " samples for each group of a ",
               kp.sizes(), " prefix cache");
   TORCH_CHECK(Pmax >= 1 && Nmax >= 1, "attention_fork: empty caches");
   TORCH_CHECK(qkv.stride(0) % 8 == 0 && aligned16(qkv), "attention_fork: 16-byte aligned rows required");
-  TORCH_CHECK(plens.device() == qkv.device() && lens.device() == qkv.device(),
-              "attention_fork: all tensors on one device");
-  TORCH_CHECK(plens.scalar_type() == torch::kInt32 && plens.is_contiguous() && plens.dim() == 1 && plens.numel() == G,
-              "attention_fork: plens must be int32 [G] on the device");
-  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() && lens.dim() == 1 && lens.numel() == R,
-              "attention_fork: lens must be int32 [R] on the device");
+  sdml::AttnForkArgs a;
+  a.plens = device_i32("attention_fork", "plens", "G", plens, G, qkv);
+  a.lens = device_i32("attention_fork", "lens", "R", lens, R, qkv);
   TORCH_CHECK(n_keys >= 1 && n_keys <= Pmax + Nmax, "attention_fork: n_keys = ", n_keys, " outside 1..", Pmax + Nmax,
               " (the prefix cache's rows plus the suffix cache's)");
   TORCH_CHECK(R <= 65535 && H >= 1 && H <= 65535, "attention_fork: rows / heads out of the grid's range");
-  sdml::AttnForkArgs a;
   a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
   auto out = torch::empty({R, C}, qkv.options());
   auto ws = torch::empty({R * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
   a.qkv = qkv.data_ptr(), a.k_prefix = kp.data_ptr(), a.v_prefix = vp.data_ptr();
   a.k_suffix = ks.data_ptr(), a.v_suffix = vs.data_ptr(), a.out = out.data_ptr();
-  a.plens = plens.data_ptr<int>(), a.lens = lens.data_ptr<int>();
   a.ws_o = ws.data_ptr<float>();
   a.ws_ml = a.ws_o + R * H * a.max_chunks * 64;
   a.G = (int)G, a.n = (int)n, a.H = (int)H, a.Pmax = (int)Pmax, a.Nmax = (int)Nmax, a.n_keys = (int)n_keys;

@@ -321,6 +321,49 @@ class GPT2Stage(PipelineStage):
         wp = _w_padded(w) if (w.is_cuda and w.dtype == torch.bfloat16) else None
         return linear_decode(y, w if wp is None else wp)
 
+    def _layers(self, x, attn, mlp):
+        """The blocks of this stage over x, without dropout: the one layer loop of the generation methods. Each residual
+        add is fused into the LayerNorm that reads its sum, as in ``forward``. ``attn(i, blk, y)`` is local block i's
+        attention branch through its ``c_proj``, ``mlp(i, blk, y)`` its MLP branch. Returns (x, y): the residual
+        stream, and what the next LayerNorm made of it (``ln_f`` on the last stage; None on a stage without blocks)."""
+        blocks = list(self.h.values())
+        y = None
+        if blocks:
+            x, y = layer_norm_pass(x, blocks[0].ln_1)
+        for i, blk in enumerate(blocks):
+            x, y = add_layer_norm(x, attn(i, blk, y), blk.ln_2)
+            m = mlp(i, blk, y)
+            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if self.is_last else None)
+            if nxt is None:
+                x = x + m
+            else:
+                x, y = add_layer_norm(x, m, nxt)
+        return x, y
+
+    def _normed(self, x, y):
+        """The last stage's ``ln_f`` rows after ``_layers``: its y, or ``ln_f(x)`` where the stage has no blocks."""
+        return self.ln_f(x) if y is None else y
+
+    @staticmethod
+    def _decode_lines(attention, tickets=None):
+        """The (attn, mlp) pair of ``_layers`` on ``linear_decode``, shared by the decode methods:
+        ``attention(i, qkv)`` is the method's own attention call on block i's fused projection; ``tickets[i]``
+        {site: counters or None} selects the one-launch forms of block i's projections."""
+        def tk(i, site):
+            return None if tickets is None else tickets[i][site]
+
+        def attn(i, blk, y):
+            at = blk.attn
+            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias, tickets=tk(i, "c_attn"))
+            return linear_decode(attention(i, qkv), at.c_proj.weight, at.c_proj.bias, tickets=tk(i, "attn_proj"))
+
+        def mlp(i, blk, y):
+            fc, pr = blk.mlp.c_fc, blk.mlp.c_proj
+            m = linear_decode(y, fc.weight, fc.bias, gelu=True, tickets=tk(i, "c_fc"))
+            return linear_decode(m, pr.weight, pr.bias, tickets=tk(i, "mlp_proj"))
+
+        return attn, mlp
+
     @torch.no_grad()
     def prefill(self, x, cache: "KVCache", lens=None, head_rows: int = 1):
         """The prompt through this stage: today's forward (flash attention at the prompt length, no dropout) plus the
@@ -343,33 +386,23 @@ class GPT2Stage(PipelineStage):
         if cache.n != 0 or S > cache.smax or B != cache.lens.shape[0]:
             raise ValueError(f"prefill of {B} x {S} tokens into a cache of {cache.lens.shape[0]} x {cache.smax} "
                              f"holding {cache.n}")
-        last = self.stage_id == self.num_stages - 1
-        blocks = list(self.h.values())
         H = self.cfg.n_head
-        y = None
-        if blocks:
-            x, y = layer_norm_pass(x, blocks[0].ln_1)
-        for i, blk in enumerate(blocks):
+
+        def attn(i, blk, y):
             qkv = blk.attn.c_attn(y)
             cache.k[i][:, :S].copy_(qkv[..., C:2 * C].view(B, S, H, C // H))
             cache.v[i][:, :S].copy_(qkv[..., 2 * C:].view(B, S, H, C // H))
-            a = blk.attn.c_proj(causal_attention(qkv, H))
-            x, y = add_layer_norm(x, a, blk.ln_2)
-            m = blk.mlp(y)
-            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
-            if nxt is None:
-                x = x + m
-            else:
-                x, y = add_layer_norm(x, m, nxt)
+            return blk.attn.c_proj(causal_attention(qkv, H))
+
+        x, y = self._layers(x, attn, lambda i, blk, y: blk.mlp(y))
         if lens is None:
             cache.lens.fill_(S)
         else:
             cache.lens.copy_(lens)
         cache.n = S
-        if not last:
+        if not self.is_last:
             return x
-        if y is None:
-            y = self.ln_f(x)
+        y = self._normed(x, y)
         if lens is None and head_rows == 1:
             return self._head_logits(y[:, -1].contiguous())
         rows = torch.arange(B, device=y.device) * S + (cache.lens.to(torch.int64) - 1)
@@ -405,28 +438,18 @@ class GPT2Stage(PipelineStage):
             pos = pos.clamp_(max=self.cfg.block_size - 1).reshape(B * T)
             x = embedding_at(x.reshape(B * T), pos, self.wte.weight, self.wpe.weight).view(B, T, -1)
         C = x.shape[-1]
-        last = self.stage_id == self.num_stages - 1
-        blocks = list(self.h.values())
         H = self.cfg.n_head
-        y = None
-        if blocks:
-            x, y = layer_norm_pass(x, blocks[0].ln_1)
-        for i, blk in enumerate(blocks):
+
+        def attn(i, blk, y):
             qkv = blk.attn.c_attn(y)
-            a = blk.attn.c_proj(attention_extend(qkv, cache.k[i], cache.v[i], cache.lens, nq, H, n_keys))
-            x, y = add_layer_norm(x, a, blk.ln_2)
-            m = blk.mlp(y)
-            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
-            if nxt is None:
-                x = x + m
-            else:
-                x, y = add_layer_norm(x, m, nxt)
+            return blk.attn.c_proj(attention_extend(qkv, cache.k[i], cache.v[i], cache.lens, nq, H, n_keys))
+
+        x, y = self._layers(x, attn, lambda i, blk, y: blk.mlp(y))
         cache.lens.add_(nq)
         cache.n = n_keys
-        if not last:
+        if not self.is_last:
             return x
-        if y is None:
-            y = self.ln_f(x)
+        y = self._normed(x, y)
         rows = torch.arange(B, device=dev) * T + (nq.to(torch.int64) - 1).clamp_(min=0)
         return self._head_logits(y.reshape(B * T, C).index_select(0, rows))
 
@@ -447,32 +470,12 @@ class GPT2Stage(PipelineStage):
             return self._decode_step_fused(x, cache)
         if self.stage_id == 0:
             x = embedding_at(x, cache.lens, self.wte.weight, self.wpe.weight)
-        last = self.stage_id == self.num_stages - 1
-        blocks = list(self.h.values())
         H = self.cfg.n_head
-        y = None
-        if blocks:
-            x, y = layer_norm_pass(x, blocks[0].ln_1)
-        for i, blk in enumerate(blocks):
-            at, mlp = blk.attn, blk.mlp
-            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias)
-            a = attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, cache.n + 1)
-            a = linear_decode(a, at.c_proj.weight, at.c_proj.bias)
-            x, y = add_layer_norm(x, a, blk.ln_2)
-            m = linear_decode(linear_decode(y, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True), mlp.c_proj.weight,
-                              mlp.c_proj.bias)
-            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
-            if nxt is None:
-                x = x + m
-            else:
-                x, y = add_layer_norm(x, m, nxt)
+        x, y = self._layers(x, *self._decode_lines(
+            lambda i, qkv: attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, cache.n + 1)))
         cache.lens.add_(1)
         cache.n += 1
-        if not last:
-            return x
-        if y is None:
-            y = self.ln_f(x)
-        return self._head_logits(y)
+        return self._head_logits(self._normed(x, y)) if self.is_last else x
 
     def fork_cache(self, cache: "KVCache", n_samples: int, nmax: int) -> "ForkedKVCache":
         """n_samples continuations of every prompt of a prefilled ``cache``: the cache itself becomes the shared
@@ -503,34 +506,14 @@ class GPT2Stage(PipelineStage):
             raise ValueError(f"the forked cache is full ({fc.n - fc.prefix.n} of {fc.nmax} suffix positions)")
         if self.stage_id == 0:
             x = embedding_at(x, fc.lens, self.wte.weight, self.wpe.weight)
-        last = self.stage_id == self.num_stages - 1
-        blocks = list(self.h.values())
         H = self.cfg.n_head
         pre = fc.prefix
-        y = None
-        if blocks:
-            x, y = layer_norm_pass(x, blocks[0].ln_1)
-        for i, blk in enumerate(blocks):
-            at, mlp = blk.attn, blk.mlp
-            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias)
-            a = attention_fork(qkv, pre.k[i], pre.v[i], pre.lens, fc.ks[i], fc.vs[i], fc.lens, fc.n_samples, H,
-                               fc.n + 1)
-            a = linear_decode(a, at.c_proj.weight, at.c_proj.bias)
-            x, y = add_layer_norm(x, a, blk.ln_2)
-            m = linear_decode(linear_decode(y, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True), mlp.c_proj.weight,
-                              mlp.c_proj.bias)
-            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
-            if nxt is None:
-                x = x + m
-            else:
-                x, y = add_layer_norm(x, m, nxt)
+        x, y = self._layers(x, *self._decode_lines(
+            lambda i, qkv: attention_fork(qkv, pre.k[i], pre.v[i], pre.lens, fc.ks[i], fc.vs[i], fc.lens,
+                                          fc.n_samples, H, fc.n + 1)))
         fc.lens.add_(1)
         fc.n += 1
-        if not last:
-            return x
-        if y is None:
-            y = self.ln_f(x)
-        return self._head_logits(y)
+        return self._head_logits(self._normed(x, y)) if self.is_last else x
 
     @torch.no_grad()
     def decode_block(self, x, cache: "KVCache", nq):
@@ -564,31 +547,12 @@ class GPT2Stage(PipelineStage):
             x = embedding_at(x.reshape(B * T), pos, self.wte.weight, self.wpe.weight)
         else:
             x = x.reshape(B * T, x.shape[-1])
-        last = self.stage_id == self.num_stages - 1
-        blocks = list(self.h.values())
         H = self.cfg.n_head
-        y = None
-        if blocks:
-            x, y = layer_norm_pass(x, blocks[0].ln_1)
-        for i, blk in enumerate(blocks):
-            at, mlp = blk.attn, blk.mlp
-            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias)
-            a = attention_append(qkv.view(B, T, -1), cache.k[i], cache.v[i], cache.lens, nq, H, n_keys)
-            a = linear_decode(a.view(B * T, -1), at.c_proj.weight, at.c_proj.bias)
-            x, y = add_layer_norm(x, a, blk.ln_2)
-            m = linear_decode(linear_decode(y, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True), mlp.c_proj.weight,
-                              mlp.c_proj.bias)
-            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
-            if nxt is None:
-                x = x + m
-            else:
-                x, y = add_layer_norm(x, m, nxt)
+        x, y = self._layers(x, *self._decode_lines(
+            lambda i, qkv: attention_append(qkv.view(B, T, -1), cache.k[i], cache.v[i], cache.lens, nq, H,
+                                            n_keys).view(B * T, -1)))
         cache.n = n_keys
-        if not last:
-            return x.view(B, T, -1)
-        if y is None:
-            y = self.ln_f(x)
-        return self._head_logits(y)
+        return self._head_logits(self._normed(x, y)) if self.is_last else x.view(B, T, -1)
 
     @torch.no_grad()
     def _decode_step_fused(self, x, cache: "KVCache", _sites=None):
@@ -602,33 +566,14 @@ class GPT2Stage(PipelineStage):
         cache.tickets.zero_()
         if self.stage_id == 0:
             x = embedding_at(x, cache.lens, self.wte.weight, self.wpe.weight)
-        last = self.stage_id == self.num_stages - 1
-        blocks = list(self.h.values())
         H = self.cfg.n_head
-        y = None
-        if blocks:
-            x, y = layer_norm_pass(x, blocks[0].ln_1)
-        for i, blk in enumerate(blocks):
-            at, mlp = blk.attn, blk.mlp
-            tk = {s: (v if s in sites else None) for s, v in views[i].items()}
-            qkv = linear_decode(y, at.c_attn.weight, at.c_attn.bias, tickets=tk["c_attn"])
-            a = attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, cache.smax, tickets=tk["attn"])
-            a = linear_decode(a, at.c_proj.weight, at.c_proj.bias, tickets=tk["attn_proj"])
-            x, y = add_layer_norm(x, a, blk.ln_2)
-            m = linear_decode(y, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True, tickets=tk["c_fc"])
-            m = linear_decode(m, mlp.c_proj.weight, mlp.c_proj.bias, tickets=tk["mlp_proj"])
-            nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else (self.ln_f if last else None)
-            if nxt is None:
-                x = x + m
-            else:
-                x, y = add_layer_norm(x, m, nxt)
+        tk = [{s: (v if s in sites else None) for s, v in d.items()} for d in views]
+        x, y = self._layers(x, *self._decode_lines(
+            lambda i, qkv: attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, cache.smax,
+                                            tickets=tk[i]["attn"]), tk))
         cache.lens.add_(1)
         cache.n += 1
-        if not last:
-            return x
-        if y is None:
-            y = self.ln_f(x)
-        return self._head_logits(y)
+        return self._head_logits(self._normed(x, y)) if self.is_last else x
 
 
 # the call sites of one block in decode_step, and those that run their one-launch form under fused=True (a site

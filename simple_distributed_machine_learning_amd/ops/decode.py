@@ -96,6 +96,12 @@ def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int, tick
     return attention_decode_ref(qkv, k_cache, v_cache, lens, n_head, n_keys)
 
 
+def _check_lens_nq(who: str, B: int, lens, nq):
+    for name, t in (("lens", lens), ("nq", nq)):
+        if t.dtype != torch.int32 or t.shape != (B,):
+            raise ValueError(f"{who}: {name} must be int32 [B], got {t.dtype} {tuple(t.shape)}")
+
+
 def attention_append_ref(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
     """The twin: query t of sample b is live iff t < nq[b] and lens[b] + t < n_keys. A live query writes its k, v at
     cache row lens[b] + t and returns softmax(q_t K[0..lens[b]+t]^T / sqrt(D)) V[0..lens[b]+t] in fp32, which is
@@ -140,9 +146,7 @@ def attention_append(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
     Smax = k_cache.shape[1]
     if not 1 <= n_keys <= Smax:
         raise ValueError(f"attention_append: n_keys = {n_keys}, but the cache has {Smax} rows")
-    for name, t in (("lens", lens), ("nq", nq)):
-        if t.dtype != torch.int32 or t.shape != (qkv.shape[0],):
-            raise ValueError(f"attention_append: {name} must be int32 [B], got {t.dtype} {tuple(t.shape)}")
+    _check_lens_nq("attention_append", qkv.shape[0], lens, nq)
     D = k_cache.shape[-1]
     if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
         return kernels().attention_append(qkv, k_cache, v_cache, lens, nq, 1.0 / math.sqrt(D), int(n_keys))
@@ -197,9 +201,7 @@ def attention_extend(qkv, k_cache, v_cache, lens, nq, n_head: int, n_keys: int):
     Smax = k_cache.shape[1]
     if not 1 <= n_keys <= Smax:
         raise ValueError(f"attention_extend: n_keys = {n_keys}, but the cache has {Smax} rows")
-    for name, t in (("lens", lens), ("nq", nq)):
-        if t.dtype != torch.int32 or t.shape != (qkv.shape[0],):
-            raise ValueError(f"attention_extend: {name} must be int32 [B], got {t.dtype} {tuple(t.shape)}")
+    _check_lens_nq("attention_extend", qkv.shape[0], lens, nq)
     D = k_cache.shape[-1]
     if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
         return kernels().attention_extend(qkv, k_cache, v_cache, lens, nq, 1.0 / math.sqrt(D), int(n_keys))
