@@ -9,6 +9,7 @@ the device to run them. Here one step is captured once with ``torch.cuda.graph``
     ``sample_step`` (the token, the token matrix, the done flags and the lengths, at device-side positions), and the
     copy of the token into the static buffer that the next replay embeds. One stream, a linear chain of nodes;
   * the stop check stays outside the graph: every ``stop_check`` steps the host reads one flag, as in the eager call.
+    The loop here checks before replay t what the eager loop (parallel/gen_common.py) checks after token t - 1.
 
 Every sampling mode goes through ``sample_step`` here (the eager call without ragged prompts, eos or top-p writes
 ``out[:, S0 + t]`` from the host, a column a graph would freeze); it draws the tokens ``sample_logits`` draws, so the
@@ -25,9 +26,11 @@ pp > 1 (a boundary crosses ranks between two kernels of the step, and a transpor
 """
 from __future__ import annotations
 
+from dataclasses import astuple, replace
+
 import torch
 
-from ..ops.decode import sample_step
+from .gen_common import Sampling, TokenState, eval_stages
 
 
 def check_graph(engine, cfg) -> None:
@@ -54,35 +57,32 @@ class DecodeSession:
         self.stage_ids = sorted(engine.stages)
         self.caches = {s: engine.stages[s].new_cache(B, total, fused=True) for s in self.stage_ids}
         self.tok = torch.zeros(B, dtype=torch.int64, device=dev)  # the token the next replay embeds
-        self.buf = torch.zeros((B, total + 1), dtype=torch.int64, device=dev)  # tokens and, last column, the lengths
-        self.out = self.buf[:, :total]
+        self.out = torch.zeros((B, total), dtype=torch.int64, device=dev)
         self.done = torch.zeros(B, dtype=torch.int32, device=dev)
         self.gen_len = torch.zeros(B, dtype=torch.int32, device=dev)
         self.graph = None
 
-    def step(self, engine, sample_kw) -> None:
+    def step(self, engine, sampling: Sampling) -> None:
         x = self.tok
         for s in self.stage_ids:
             if self._sites is None:
                 x = engine.stages[s].decode_step(x, self.caches[s], fused=True)
             else:
                 x = engine.stages[s]._decode_step_fused(x, self.caches[s], _sites=self._sites)
-        tok = sample_step(x, positions=self.caches[self.stage_ids[-1]].lens, out=self.out, done=self.done,
-                          gen_len=self.gen_len, **sample_kw)
-        self.tok.copy_(tok)
+        self.tok.copy_(sampling.step(x, self.caches[self.stage_ids[-1]].lens, self))
 
-    def capture(self, engine, sample_kw) -> None:
+    def capture(self, engine, sampling: Sampling) -> None:
         """One eager step on the capture stream (every kernel of the step has run once before the capture; the state
         it touches is the empty caches' row 0 and the buffers, which every call initialises), then the capture."""
         stream = torch.cuda.Stream(device=engine.device)
         stream.wait_stream(torch.cuda.current_stream(engine.device))
         with torch.cuda.stream(stream):
-            self.step(engine, sample_kw)
+            self.step(engine, sampling)
         torch.cuda.current_stream(engine.device).wait_stream(stream)
         self.reset()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, stream=stream):
-            self.step(engine, sample_kw)
+            self.step(engine, sampling)
         engine.decode_graph_captures += 1
 
     def reset(self) -> None:
@@ -104,55 +104,31 @@ def _param_addresses(engine):
 
 
 @torch.no_grad()
-def generate_graphed(engine, prompts, cfg, new: int, temperature, top_k, nseed, sample0, top_p, lens_host, eos_token,
-                     pad_token, stop_check, return_lengths):
-    """generate()'s body for ``graph=True`` on one rank holding every stage; the arguments are already checked."""
-    dev = engine.device
-    B, S0 = prompts.shape
-    total = S0 + new
-    eos = -1 if eos_token is None else int(eos_token)
-    pad = int(pad_token)
-    sample_kw = dict(vocab=cfg.vocab_size, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
-                     seed=nseed, sample0=int(sample0), eos=eos, pad=pad)
-    key = (B, total, float(temperature), int(top_k), float(top_p), nseed, int(sample0), eos, pad,
-           _param_addresses(engine))
+def generate_graphed(engine, prompts, lens_host, new: int, sampling: Sampling, check: int):
+    """generate()'s driver for ``graph=True`` on one rank holding every stage; the arguments are already checked.
+    Returns (tokens, lengths, prompt lengths, steps)."""
+    B, total = prompts.shape[0], prompts.shape[1] + new
+    sp = replace(sampling, temperature=float(sampling.temperature), top_k=int(sampling.top_k),
+                 top_p=float(sampling.top_p), sample0=int(sampling.sample0))
+    key = (B, total) + astuple(sp)[1:] + (_param_addresses(engine),)
     stage_ids = sorted(engine.stages)
-    was_training = {s: engine.stages[s].training for s in stage_ids}
-    for s in stage_ids:
-        engine.stages[s].eval()
-    try:
+    with eval_stages([engine.stages[s] for s in stage_ids]):
         ses = engine.decode_session
         if ses is None or ses.key != key:
             engine.decode_session = None  # (the old session's memory goes before the new one's is taken)
             del ses
             ses = DecodeSession(engine, key, B, total)
-            ses.capture(engine, sample_kw)
+            ses.capture(engine, sp)
             engine.decode_session = ses
         ses.reset()
-        prompts = prompts.to(dev)
-        lens0 = torch.tensor(lens_host if lens_host is not None else [S0] * B, dtype=torch.int64, device=dev)
-        out, buf = ses.out, ses.buf
-        out.fill_(pad)
-        out[:, :S0] = torch.where(torch.arange(S0, device=dev)[None, :] < lens0[:, None], prompts,
-                                  torch.full_like(prompts, pad))
-        prompts = out[:, :S0].contiguous()
-        lens_dev = lens0.to(torch.int32) if lens_host is not None else None
+        st = TokenState(prompts, lens_host, total, sp.pad, engine.device, storage=(ses.out, ses.done, ses.gen_len))
         # the prompt and the first token: eager, into the session's caches and buffers
-        x = prompts
+        x = st.prompts
         for s in stage_ids:
-            mod = engine.stages[s]
-            x = mod.prefill(x, ses.caches[s]) if lens_dev is None else mod.prefill(x, ses.caches[s], lens=lens_dev)
-        tok = sample_step(x, positions=ses.caches[stage_ids[-1]].lens, out=out, done=ses.done, gen_len=ses.gen_len,
-                          **sample_kw)
-        ses.tok.copy_(tok)
-        check = int(stop_check) if eos_token is not None else 0
-        for t in range(1, new):  # token index S0 + t (ragged: lens[b] + t)
+            x = engine.stages[s].prefill(x, ses.caches[s], lens=st.lens_dev)
+        ses.tok.copy_(sp.step(x, ses.caches[stage_ids[-1]].lens, ses))
+        for t in range(1, new):  # token index S0 + t (ragged: lens[b] + t); decode_loop's check after token t - 1
             if check and t % check == 0 and bool(ses.done.min().item()):
                 break
             ses.replay()
-        buf[:, total] = lens0 + ses.gen_len
-    finally:
-        for s in stage_ids:
-            engine.stages[s].train(was_training[s])
-    res = out.contiguous()
-    return (res, buf[:, total].clone()) if return_lengths else res
+        return ses.out.clone(), st.lengths(), st.lens0, 0  # (no step count: stats are refused with a graph)

@@ -53,15 +53,22 @@ the bubble and are not implemented. ``graph=True`` is refused with pp > 1: the s
 kernels, and a transport call cannot be part of a captured graph. ``lookup > 0`` is refused with ``graph=True`` (the
 verify step is not captured yet) and with pp > 1 (the other ranks' caches would need the accepted counts); on the
 kernels B * (K + 1) may not exceed 64 rows.
+
+``generate()`` itself checks the arguments and hands the call to one driver: ``_generate_pipeline`` (the plain loop),
+``_generate_lookup``, ``_generate_forked``, ``_generate_chunked`` or decode_graph's ``generate_graphed``. The token
+state, the sampling arguments, the decode loop and the form of the result are one copy, parallel/gen_common.py.
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import Optional
 
 import torch
 
-from ..ops.decode import (ATTENTION_FORK_MAX_N, LINEAR_DECODE_MAX_M, LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, lookup_step,
-                          sample_logits, sample_step)
+from ..ops.decode import ATTENTION_FORK_MAX_N, LINEAR_DECODE_MAX_M, LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, lookup_step
+from .decode_graph import check_graph, generate_graphed
+from .gen_common import Sampling, TokenState, decode_loop, eval_stages, result
+from .session import GenerationSession
 
 # message tags no schedule produces: message_tag() keeps mb * 4096 + stage in the bits above 2, and a schedule's
 # stage index is far below 4095
@@ -111,8 +118,10 @@ def pad_prompts(prompts, pad_token: int = 0):
     return t, torch.tensor([len(r) for r in rows], dtype=torch.int32)
 
 
-def _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check):
-    """The refusals of the new arguments; returns the prompt lengths as a list (None: one length)."""
+def _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check, temperature=0.0):
+    """The refusals of the sampling arguments; returns the prompt lengths as a list (None: one length)."""
+    if temperature < 0:
+        raise ValueError(f"generate: temperature must be >= 0, got {temperature}")
     if not 0.0 <= float(top_p) <= 1.0:
         raise ValueError(f"generate: top_p must be in [0, 1], got {top_p}")
     V = cfg.vocab_size
@@ -154,24 +163,14 @@ def _check_lookup(engine, cfg, B: int, lookup, lookup_ngram, graph: bool):
                          f"verify step, but the decode projections take at most {LINEAR_DECODE_MAX_M}")
 
 
-def _generate_chunked(engine, prompts, new, temperature, top_k, seed, sample0, top_p, lens_host, eos_token, pad_token,
-                      stop_check, return_lengths, return_stats, prefill_chunk):
-    """generate() with ``prefill_chunk`` > 0: a session of this call's length, its result in generate()'s form."""
-    from .session import GenerationSession
-
-    B, S0 = prompts.shape
-    s = GenerationSession(engine, prompts, S0 + new, prompt_lens=lens_host, pad_token=pad_token, seed=seed,
-                          sample0=sample0)
+def _generate_chunked(engine, prompts, lens_host, new: int, sp: Sampling, check: int, prefill_chunk: int):
+    """The driver of ``prefill_chunk`` > 0: a session of this call's length (parallel/session.py), run once. ``sp``
+    carries this call's seed, so the session needs none of its own."""
+    s = GenerationSession(engine, prompts, prompts.shape[1] + new, lens_host, sp.pad, sample0=sp.sample0)
     lens0 = s.lengths.to(torch.int64)
-    res, lengths = s.generate(new, temperature, top_k, top_p, eos_token, stop_check, prefill_chunk)
-    steps = s.steps
+    out, lengths = s.run(new, sp, check, prefill_chunk)
     s.close()
-    res = (res, lengths) if return_lengths else res
-    if return_stats:
-        generated = lengths - lens0
-        res = (res if isinstance(res, tuple) else (res,)) + ({"steps": steps, "row_steps": generated.clone(),
-                                                              "generated": generated},)
-    return res
+    return out, lengths, lens0, s.steps
 
 
 def _check_samples(engine, num_samples, graph: bool, lookup: int, prefill_chunk: int):
@@ -190,171 +189,75 @@ def _check_samples(engine, num_samples, graph: bool, lookup: int, prefill_chunk:
             raise ValueError(f"generate: num_samples > 1 is not supported with {what}")
 
 
-def _generate_forked(engine, prompts, cfg, new: int, temperature, top_k, nseed: int, sample0: int, top_p, lens_host,
-                     eos_token, pad_token, stop_check, return_lengths: bool, return_stats: bool, n: int):
-    """generate() with ``num_samples`` = n > 1 (one rank): the B prompts are prefilled once, every local stage's cache
-    is forked (models/gpt2.py fork_cache) and the B n rows decode through ``decode_step_forked``. Row b n + j is
-    sibling j of prompt b and sample ``sample0 + b n + j`` of the sampler, so tokens, lengths and stats are those of
-    the call on ``prompts.repeat_interleave(n, 0)``, bit for bit: the sampler lines below are that call's."""
-    dev, P = engine.device, engine.P
-    B, S0 = prompts.shape
-    R, total = B * n, S0 + new
-    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0
-    prompts = prompts.to(dev)
-    lens_b = torch.tensor(lens_host if lens_host is not None else [S0] * B, dtype=torch.int64, device=dev)
-    if stepped:  # (the padding holds the pad token, whatever the caller left there)
-        prompts = torch.where(torch.arange(S0, device=dev)[None, :] < lens_b[:, None], prompts,
-                              torch.full_like(prompts, int(pad_token)))
-    lens0 = lens_b.repeat_interleave(n)
-    out = torch.full((R, total), int(pad_token), dtype=torch.int64, device=dev)
-    out[:, :S0] = prompts.repeat_interleave(n, 0)
-    done = torch.zeros(R, dtype=torch.int32, device=dev)
-    gen_len = torch.zeros(R, dtype=torch.int32, device=dev)
-    eos = -1 if eos_token is None else int(eos_token)
-    check = int(stop_check) if eos_token is not None else 0
-    steps_run = 0
-    if new > 0:
-        stages = [engine.stages[s] for s in range(P)]
-        was_training = [m.training for m in stages]
-        for m in stages:
-            m.eval()
-        try:
-            lens_dev = lens_b.to(torch.int32) if lens_host is not None else None
-            caches = [m.new_cache(B, S0) for m in stages]  # the shared prefixes: the prompt's rows and no more
-            x = prompts
-            for s, m in enumerate(stages):
-                x = m.prefill(x, caches[s], lens=lens_dev, head_rows=n if s == P - 1 else 1)
-            forks = [m.fork_cache(caches[s], n, new) for s, m in enumerate(stages)]
-            lens = forks[P - 1].lens
-            for t in range(new):  # token index S0 + t (ragged: lens[r] + t)
-                if t > 0:
-                    for s, m in enumerate(stages):
-                        x = m.decode_step_forked(x, forks[s])
-                if stepped:
-                    x = sample_step(x, cfg.vocab_size, temperature, top_k, top_p, nseed, sample0, lens, out, done,
-                                    gen_len, eos, int(pad_token))
-                else:
-                    x = sample_logits(x, cfg.vocab_size, temperature, top_k, nseed, sample0, lens)
-                    out[:, S0 + t] = x
-                if check and (t + 1) % check == 0 and t + 1 < new and bool(done.min().item()):
-                    break
-            steps_run = t + 1
-        finally:
-            for m, tr_ in zip(stages, was_training):
-                m.train(tr_)
-    lengths = lens0 + gen_len if stepped else torch.full((R,), total, dtype=torch.int64, device=dev)
-    res = (out, lengths) if return_lengths else out
-    if return_stats:
-        generated = lengths - lens0 if stepped else torch.full((R,), new, dtype=torch.int64, device=dev)
-        stats = {"steps": steps_run, "row_steps": generated.clone(), "generated": generated}
-        res = (res if isinstance(res, tuple) else (res,)) + (stats,)
-    return res
+def _generate_forked(engine, st: TokenState, sp: Sampling, new: int, check: int, n: int):
+    """The driver of ``num_samples`` = n > 1 (one rank): the B prompts are prefilled once, every stage's cache is forked
+    (models/gpt2.py fork_cache) and the B n rows decode through ``decode_step_forked``. Row b n + j is sibling j of
+    prompt b and sample ``sample0 + b n + j`` of the sampler: ``st`` holds the rows of the call on
+    ``prompts.repeat_interleave(n, 0)``, and the sampler and the loop are that call's, so its bits are too."""
+    P = engine.P
+    stages = [engine.stages[s] for s in range(P)]
+    with eval_stages(stages):
+        caches = [m.new_cache(*st.prompts.shape) for m in stages]  # the shared prefixes: the prompt's rows and no more
+        x = st.prompts
+        for s, m in enumerate(stages):
+            x = m.prefill(x, caches[s], lens=st.lens_dev, head_rows=n if s == P - 1 else 1)
+        forks = [m.fork_cache(caches[s], n, new) for s, m in enumerate(stages)]
+
+        def advance(x, t):
+            for m, fork in zip(stages, forks):
+                x = m.decode_step_forked(x, fork)
+            return x
+        steps = decode_loop(x, new, check, st.sampler(sp, forks[P - 1].lens), advance,
+                            lambda: bool(st.done.min().item()))
+    return st.out, st.lengths(), st.lens0, steps
 
 
-@torch.no_grad()
-def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
-             seed: Optional[int] = None, sample0: int = 0, top_p: float = 1.0, prompt_lens=None,
-             eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
-             graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False,
-             prefill_chunk: int = 0, num_samples: int = 1):
-    """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
-    ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
-    samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
-    ``pad_prompts``): ragged prompts, every row generating up to ``max_new_tokens`` tokens from its own length on.
-    ``eos_token``: a row stops after drawing it; what follows is ``pad_token``. ``stop_check``: with an eos, the host
-    asks every that many steps whether all rows are done (0: never; the result does not depend on it).
-    ``return_lengths``: (tokens, lengths int64 [B]), a row's prompt plus its generated tokens, the eos included.
-    ``graph``: replay one captured decode step per token (parallel/decode_graph.py; the same tokens and lengths). The
-    session stays on the engine, so the next call of the same shape and sampling arguments captures nothing.
-    ``lookup`` = K in 1..7: prompt-lookup speculation with K drafts per row and step, matched on the row's last
-    ``lookup_ngram`` tokens (module docstring); the same tokens and lengths in fewer steps. ``stop_check`` then counts
-    verify steps and is honoured without an eos too. ``return_stats``: a dict is appended to the result, ``steps`` (the
-    host's loop count), ``row_steps`` and ``generated`` (int64 [B] on the device: the steps in which the row emitted a
-    token, and its generated tokens). ``prefill_chunk`` = P > 0 (one rank, not with ``graph`` or ``lookup``): the prompt
-    goes through ``extend`` in chunks of P positions instead of one ``prefill`` pass, on a ``GenerationSession``
-    (parallel/session.py) that lives for this call; 0 runs the lines it always ran. ``num_samples`` = n in 2..64 (one
-    rank, not with ``graph``, ``lookup`` or ``prefill_chunk``): n continuations of every prompt from one prefill and
-    one copy of the prompt's keys; the result has B n rows, row b n + j sibling j of prompt b, and is that of the call
-    on ``prompts.repeat_interleave(n, 0)`` bit for bit (module docstring); 1 runs the lines it always ran."""
-    from ..models.gpt2 import dropout_seed
+def _generate_lookup(engine, st: TokenState, sp: Sampling, new: int, every: int, K: int, ngram: int):
+    """The driver of ``lookup`` = K > 0 (one rank): the prefill and the first token as always, then verify steps of
+    K + 1 positions per row; every ``every`` steps the host reads one flag (are all rows done or full?)."""
+    stages = [engine.stages[s] for s in range(engine.P)]
+    B, T, dev = st.prompts.shape[0], K + 1, engine.device
+    row_steps = torch.zeros(B, dtype=torch.int32, device=dev)
+    steps = 0
+    with eval_stages(stages):
+        caches = [m.new_cache(B, st.total) for m in stages]
+        lens = caches[0].lens
+        for c in caches[1:]:  # decode_block leaves the lengths to lookup_step: the stages read one tensor
+            c.lens = lens
+        x = st.prompts
+        for m, c in zip(stages, caches):
+            x = m.prefill(x, c, lens=st.lens_dev)
+        sp.step(x, lens, st)
+        # from here on lens[b] is the column of row b's newest token, which is not in the cache yet
+        limit = (st.lens0 + new).to(torch.int32)
+        nxt, nq, flag = lookup_step(None, None, None, st.out, lens, limit, st.done, st.gen_len, row_steps, K, ngram,
+                                    sp.eos, sp.pad)
+        offs = torch.arange(1, T + 1, dtype=torch.int32, device=dev)[None, :]
+        for steps in range(1, new):
+            x = nxt
+            for m, c in zip(stages, caches):
+                x = m.decode_block(x, c, nq)
+            pos = (lens[:, None] + offs).reshape(B * T)  # the token drawn at row (b, t) sits at lens[b] + t + 1
+            g = sp.draw(x, pos, T)
+            nxt, nq, flag = lookup_step(g.view(B, T), nxt, nq, st.out, lens, limit, st.done, st.gen_len, row_steps, K,
+                                        ngram, sp.eos, sp.pad)
+            if every and steps % every == 0 and steps < new - 1 and bool(flag.item()):
+                break
+    return st.out, st.lengths(), st.lens0, steps, row_steps
 
-    prompts, cfg = _check(engine, prompts, int(max_new_tokens))
-    if temperature < 0:
-        raise ValueError(f"generate: temperature must be >= 0, got {temperature}")
-    lens_host = _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check)
-    _check_lookup(engine, cfg, prompts.shape[0], lookup, lookup_ngram, graph)
-    if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 0:
-        raise ValueError(f"generate: prefill_chunk must be an integer >= 0, got {prefill_chunk!r}")
-    if prefill_chunk > 0 and (graph or lookup > 0):
-        raise ValueError("generate: prefill_chunk > 0 with graph=True or lookup > 0 is not supported (the chunked "
-                         "prefill runs on a session, which neither path drives yet)")
-    if return_stats and graph:
-        raise ValueError("generate: return_stats is not available with graph=True")
-    _check_samples(engine, num_samples, graph, lookup, prefill_chunk)
-    if num_samples > 1:
-        return _generate_forked(engine, prompts, cfg, int(max_new_tokens), temperature, top_k,
-                                dropout_seed(0 if seed is None else seed), sample0, top_p, lens_host, eos_token,
-                                pad_token, stop_check, return_lengths, return_stats, num_samples)
-    if prefill_chunk > 0:
-        return _generate_chunked(engine, prompts, int(max_new_tokens), temperature, top_k, seed, sample0, top_p,
-                                 lens_host, eos_token, pad_token, stop_check, return_lengths, return_stats,
-                                 prefill_chunk)
-    if graph:
-        from .decode_graph import check_graph, generate_graphed
 
-        check_graph(engine, cfg)
-        if int(max_new_tokens) > 0:
-            return generate_graphed(engine, prompts, cfg, int(max_new_tokens), temperature, top_k,
-                                    dropout_seed(0 if seed is None else seed), sample0, top_p, lens_host, eos_token,
-                                    pad_token, stop_check, return_lengths)
-    # the step kernel (sample + bookkeeping in one launch) serves the new arguments; without them: the lines below
-    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0 or lookup > 0
+def _generate_pipeline(engine, cfg, st: TokenState, sp: Sampling, new: int, check: int):
+    """The plain driver, on every rank of the pipeline (module docstring)."""
     mesh, dev, P = engine.mesh, engine.device, engine.P
     sched = engine.schedule(1, True)
     owner = [sched.stage_rank(0, s) for s in range(P)]  # pipeline rank of each stage
     me = mesh.pp_rank
     grank = lambda r: mesh.global_rank(mesh.dp_rank, r)  # noqa: E731
     tr = engine.transport
-    B, S0 = prompts.shape
-    new = int(max_new_tokens)
-    total = S0 + new
-    prompts = prompts.to(dev)
-    # tokens and, in a last column, the lengths: one buffer, so the final broadcast carries both
-    buf = torch.empty((B, total + 1), dtype=torch.int64, device=dev)
-    out = buf[:, :total]
-    lens0 = torch.tensor(lens_host if lens_host is not None else [S0] * B, dtype=torch.int64, device=dev)
-    if stepped:
-        out.fill_(int(pad_token))
-        out[:, :S0] = torch.where(torch.arange(S0, device=dev)[None, :] < lens0[:, None], prompts,
-                                  torch.full_like(prompts, int(pad_token)))
-        prompts = out[:, :S0].contiguous()  # (the padding holds the pad token, whatever the caller left there)
-    else:
-        out[:, :S0] = prompts
-    buf[:, total] = lens0 if stepped else total
-    if new == 0:
-        res = out.contiguous()
-        res = (res, buf[:, total].clone()) if return_lengths else res
-        if return_stats:
-            zeros = torch.zeros(B, dtype=torch.int64, device=dev)
-            res = (res if isinstance(res, tuple) else (res,)) + ({"steps": 0, "row_steps": zeros, "generated": zeros},)
-        return res
-    nseed = dropout_seed(0 if seed is None else seed)
+    (B, S0), total = st.prompts.shape, st.total
     mine = [s for s in range(P) if owner[s] == me and s in engine.stages]
-    was_training = {s: engine.stages[s].training for s in mine}
-    for s in mine:
-        engine.stages[s].eval()
-    caches = {s: engine.stages[s].new_cache(B, total) for s in mine}
-    if lookup:  # decode_block leaves the lengths to lookup_step: this rank's stages read one tensor
-        for s in mine[1:]:
-            caches[s].lens = caches[mine[0]].lens
-    dt = engine.dtype
-    C = cfg.n_embd
+    dt, C = engine.dtype, cfg.n_embd
     first, last = owner[0], owner[P - 1]
-    lens_dev = lens0.to(torch.int32) if lens_host is not None else None
-    done = torch.zeros(B, dtype=torch.int32, device=dev)
-    gen_len = torch.zeros(B, dtype=torch.int32, device=dev)
-    eos = -1 if eos_token is None else int(eos_token)
-    check = int(stop_check) if eos_token is not None else 0
 
     def run_stages(x, step: int, prefill: bool):
         """Run this rank's stages in order for one prefill / decode step; x: stage 0's input where this rank holds it.
@@ -369,12 +272,7 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
                 tr.irecv(buf_, grank(owner[s - 1]), _tag(PL_GEN_ACT, s, step)).wait()
                 x = buf_
             mod = engine.stages[s]
-            if not prefill:
-                x = mod.decode_step(x, caches[s])
-            elif lens_dev is None:
-                x = mod.prefill(x, caches[s])
-            else:
-                x = mod.prefill(x, caches[s], lens=lens_dev)
+            x = mod.prefill(x, caches[s], lens=st.lens_dev) if prefill else mod.decode_step(x, caches[s])
             if s == P - 1:
                 res = x
             elif owner[s + 1] != me:
@@ -405,78 +303,90 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
         """The one host read of the stop check: are all rows done? The last stage's rank holds the flags; in a
         pipeline every rank learns the answer through the pipeline group (the others add zeros)."""
         if mesh.pp == 1 or tr is None:
-            return bool(done.min().item())
-        flag = done.min().to(torch.int64).reshape(1) if me == last else torch.zeros(1, dtype=torch.int64, device=dev)
+            return bool(st.done.min().item())
+        flag = st.done.min().to(torch.int64).reshape(1) if me == last else torch.zeros(1, dtype=torch.int64, device=dev)
         tr.all_reduce(flag, channel="fwd", async_op=False)
         return bool(flag.item())
 
-    def lookup_loop() -> int:
-        """lookup > 0 (one rank): the prefill and the first token as always, then verify steps of K + 1 positions per
-        row. Returns the number of verify steps run."""
-        K, T = int(lookup), int(lookup) + 1
-        cache = caches[P - 1]
-        logits = run_stages(prompts, 0, prefill=True)
-        sample_step(logits, cfg.vocab_size, temperature, top_k, top_p, nseed, sample0, cache.lens, out, done, gen_len,
-                    eos, int(pad_token))
-        # from here on lens[b] is the column of row b's newest token, which is not in the cache yet
-        limit = (lens0 + new).to(torch.int32)
-        nxt, nq, flag = lookup_step(None, None, None, out, cache.lens, limit, done, gen_len, row_steps, K,
-                                    int(lookup_ngram), eos, int(pad_token))
-        offs = torch.arange(1, T + 1, dtype=torch.int32, device=dev)[None, :]
-        every = int(stop_check)
-        steps = 0
-        for it in range(new - 1):
-            x = nxt
-            for s in range(P):
-                x = engine.stages[s].decode_block(x, caches[s], nq)
-            pos = (cache.lens[:, None] + offs).reshape(B * T)  # the token drawn at row (b, t) sits at lens[b] + t + 1
-            g = sample_step(x, cfg.vocab_size, temperature, top_k, top_p, nseed, sample0, pos, rows_per_sample=T)
-            nxt, nq, flag = lookup_step(g.view(B, T), nxt, nq, out, cache.lens, limit, done, gen_len, row_steps, K,
-                                        int(lookup_ngram), eos, int(pad_token))
-            steps += 1
-            if every and steps % every == 0 and it + 1 < new - 1 and bool(flag.item()):
-                break
-        return steps
+    def advance(tok, t: int):
+        tok = exchange_token(tok, t)
+        return run_stages(tok if me == first else None, t + 1, prefill=False)
 
-    row_steps = torch.zeros(B, dtype=torch.int32, device=dev)
-    steps_run = 0
-    try:
-        tok = None
-        if lookup:
-            steps_run = lookup_loop()
-        # the plain loop (skipped after a lookup run): token index S0 + t (ragged: lens[b] + t)
-        for t in range(0 if lookup else new):
-            x = (prompts if t == 0 else tok) if me == first else None
-            logits = run_stages(x, t, prefill=(t == 0))
-            if me == last:
-                cache = caches[P - 1]
-                if stepped:
-                    tok = sample_step(logits, cfg.vocab_size, temperature, top_k, top_p, nseed, sample0, cache.lens,
-                                      out, done, gen_len, eos, int(pad_token))
-                else:
-                    tok = sample_logits(logits, cfg.vocab_size, temperature, top_k, nseed, sample0, cache.lens)
-                    out[:, S0 + t] = tok
-            if check and (t + 1) % check == 0 and t + 1 < new and all_done():
-                break
-            if t + 1 < new:
-                tok = exchange_token(tok, t)
-        if not lookup:
-            steps_run = t + 1
-        if stepped and me == last:
-            buf[:, total] = lens0 + gen_len
+    with eval_stages([engine.stages[s] for s in mine]):
+        caches = {s: engine.stages[s].new_cache(B, total) for s in mine}
+        # token index S0 + t (ragged: lens[b] + t); only the last stage's rank samples
+        sample = st.sampler(sp, caches[P - 1].lens) if me == last else lambda logits, t: None
+        logits = run_stages(st.prompts if me == first else None, 0, prefill=True)
+        steps = decode_loop(logits, new, check, sample, advance, all_done)
+        out, lengths = st.out, st.lengths()
         if tr is not None:
             tr.drain_sends()
-            if mesh.pp > 1:  # the last stage's rank holds the tokens: everyone gets them
-                mask = buf if me == last else buf.zero_()
-                tr.all_reduce(mask, channel="fwd", async_op=False)
-    finally:
-        for s in mine:
-            engine.stages[s].train(was_training[s])
-    res = out.contiguous()
-    res = (res, buf[:, total].clone()) if return_lengths else res
-    if return_stats:
-        generated = buf[:, total] - lens0 if stepped else torch.full((B,), new, dtype=torch.int64, device=dev)
-        stats = {"steps": steps_run, "row_steps": row_steps.to(torch.int64) if lookup else generated.clone(),
-                 "generated": generated}
-        res = (res if isinstance(res, tuple) else (res,)) + (stats,)
-    return res
+            if mesh.pp > 1:  # the last stage's rank holds the tokens and the lengths: everyone gets them, in one sum
+                buf = torch.cat([out, lengths[:, None]], 1) if me == last else \
+                    torch.zeros((B, total + 1), dtype=torch.int64, device=dev)
+                tr.all_reduce(buf, channel="fwd", async_op=False)
+                out, lengths = buf[:, :total].contiguous(), buf[:, total].clone()
+    return out, lengths, st.lens0, steps
+
+
+@torch.no_grad()
+def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
+             seed: Optional[int] = None, sample0: int = 0, top_p: float = 1.0, prompt_lens=None,
+             eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
+             graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False,
+             prefill_chunk: int = 0, num_samples: int = 1):
+    """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
+    ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
+    samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
+    ``pad_prompts``): ragged prompts, every row generating up to ``max_new_tokens`` tokens from its own length on.
+    ``eos_token``: a row stops after drawing it; what follows is ``pad_token``. ``stop_check``: with an eos, the host
+    asks every that many steps whether all rows are done (0: never; the result does not depend on it).
+    ``return_lengths``: (tokens, lengths int64 [B]), a row's prompt plus its generated tokens, the eos included.
+    ``graph``: replay one captured decode step per token (parallel/decode_graph.py; the same tokens and lengths). The
+    session stays on the engine, so the next call of the same shape and sampling arguments captures nothing.
+    ``lookup`` = K in 1..7: prompt-lookup speculation with K drafts per row and step, matched on the row's last
+    ``lookup_ngram`` tokens (module docstring); the same tokens and lengths in fewer steps. ``stop_check`` then counts
+    verify steps and is honoured without an eos too. ``return_stats``: a dict is appended to the result, ``steps`` (the
+    host's loop count), ``row_steps`` and ``generated`` (int64 [B] on the device: the steps in which the row emitted a
+    token, and its generated tokens). ``prefill_chunk`` = P > 0 (one rank, not with ``graph`` or ``lookup``): the prompt
+    goes through ``extend`` in chunks of P positions instead of one ``prefill`` pass, on a ``GenerationSession``
+    (parallel/session.py) that lives for this call; 0 runs the lines it always ran. ``num_samples`` = n in 2..64 (one
+    rank, not with ``graph``, ``lookup`` or ``prefill_chunk``): n continuations of every prompt from one prefill and
+    one copy of the prompt's keys; the result has B n rows, row b n + j sibling j of prompt b, and is that of the call
+    on ``prompts.repeat_interleave(n, 0)`` bit for bit (module docstring); 1 runs the lines it always ran."""
+    from ..models.gpt2 import dropout_seed
+
+    new = int(max_new_tokens)
+    prompts, cfg = _check(engine, prompts, new)
+    lens_host = _check_step(cfg, prompts, top_p, prompt_lens, eos_token, pad_token, stop_check, temperature)
+    _check_lookup(engine, cfg, prompts.shape[0], lookup, lookup_ngram, graph)
+    if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 0:
+        raise ValueError(f"generate: prefill_chunk must be an integer >= 0, got {prefill_chunk!r}")
+    if prefill_chunk > 0 and (graph or lookup > 0):
+        raise ValueError("generate: prefill_chunk > 0 with graph=True or lookup > 0 is not supported (the chunked "
+                         "prefill runs on a session, which neither path drives yet)")
+    if return_stats and graph:
+        raise ValueError("generate: return_stats is not available with graph=True")
+    _check_samples(engine, num_samples, graph, lookup, prefill_chunk)
+    if graph:
+        check_graph(engine, cfg)
+    sp = Sampling(cfg.vocab_size, temperature, top_k, top_p, dropout_seed(0 if seed is None else seed), sample0,
+                  -1 if eos_token is None else int(eos_token), int(pad_token))
+    check = int(stop_check) if eos_token is not None else 0
+    # the step kernel (sample + bookkeeping in one launch) serves these arguments; without them the host stores a column
+    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0
+    state = partial(TokenState, prompts, lens_host, prompts.shape[1] + new, sp.pad, engine.device)
+    if prefill_chunk > 0:
+        res = _generate_chunked(engine, prompts, lens_host, new, sp, check, prefill_chunk)
+    elif new == 0:  # nothing to draw in any other mode: the prompts come back, cleaned where the mode steps
+        st = state(stepped=stepped or lookup > 0, repeat=num_samples)
+        res = st.out, st.lengths(), st.lens0, 0
+    elif num_samples > 1:
+        res = _generate_forked(engine, state(stepped=stepped, repeat=num_samples), sp, new, check, num_samples)
+    elif graph:
+        res = generate_graphed(engine, prompts, lens_host, new, sp, check)
+    elif lookup > 0:
+        res = _generate_lookup(engine, state(), sp, new, int(stop_check), lookup, lookup_ngram)
+    else:
+        res = _generate_pipeline(engine, cfg, state(stepped=stepped), sp, new, check)
+    return result(*res[:3], return_lengths, return_stats, *res[3:])

@@ -25,8 +25,9 @@ cache.lens[b]) and keeps the logits of each row's last token:
   * otherwise ``extend`` over chunks of P positions, P = ``prefill_chunk`` or max u_b: chunk c carries
     clamp(u_b - c P, 0, P) positions of each row, counted from the row's own cached length, and a row keeps the logits
     of the chunk that held its last token (a select on the device).
-Then the loop of ``generate()``: ``sample_step`` (token, its place in ``out``, the length, the done flag on the eos),
-``decode_step``, and with an eos the stop check every ``stop_check`` steps.
+Then the loop of ``generate()`` itself (parallel/gen_common.py ``decode_loop``; the session is the sampler's token
+state, ``gen_len`` its ``lengths``): ``sample_step`` (token, its place in ``out``, the length, the done flag on the
+eos), ``decode_step``, and with an eos the stop check every ``stop_check`` steps.
 
 Host synchronisation: one read of ``lengths`` / ``done`` at the end of a ``generate`` call (plus the stop checks with an
 eos), none per step. It makes the host's bounds exact: ``append`` and the next ``generate`` check against ``max_len``
@@ -42,7 +43,7 @@ from typing import Optional
 
 import torch
 
-from ..ops.decode import sample_step
+from .gen_common import Sampling, clean_prompts, decode_loop, eval_stages
 
 
 def _as_rows(tokens, lens, B: int, what: str):
@@ -94,18 +95,17 @@ class GenerationSession:
         self._cached_h = [0] * B
         self._done_h = [False] * B
         self._fresh = True  # every cache empty
-        self.lengths = torch.tensor(self._len_h, dtype=torch.int32, device=dev)
+        self.lengths = self.gen_len = torch.tensor(self._len_h, dtype=torch.int32, device=dev)
         self.done = torch.zeros(B, dtype=torch.int32, device=dev)
         self.out = torch.full((B, max_len), self.pad_token, dtype=torch.int64, device=dev)
-        live = torch.arange(S0, device=dev)[None, :] < self.lengths[:, None]
-        self.out[:, :S0] = torch.where(live, prompts.to(dev), self.out[:, :S0])
+        self.out[:, :S0] = clean_prompts(prompts.to(dev), self.lengths, self.out[:, :S0])
         self.stages = [engine.stages[s] for s in range(engine.P)]
         self.caches = [m.new_cache(B, max_len) for m in self.stages]
         self.steps = 0  # decode loop steps of the last generate call
 
     def close(self):
         """Drop the caches and the token matrix; the session takes no further calls."""
-        self.caches = self.out = self.lengths = self.done = None
+        self.caches = self.out = self.lengths = self.gen_len = self.done = None
 
     def _open(self, what: str):
         if self.caches is None:
@@ -206,7 +206,6 @@ class GenerationSession:
         self._cached_h = [ch + (0 if d else 1) for ch, d in zip(self._cached_h, self._done_h)]
         return logits
 
-    @torch.no_grad()
     def generate(self, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  eos_token: Optional[int] = None, stop_check: int = 16, prefill_chunk: int = 0):
         """Up to ``max_new_tokens`` more tokens per row that is not done; returns (tokens int64 [B, max_len], lengths
@@ -216,41 +215,34 @@ class GenerationSession:
 
         self._open("generate")
         new = int(max_new_tokens)
-        if temperature < 0:
-            raise ValueError(f"generate: temperature must be >= 0, got {temperature}")
         if int(prefill_chunk) < 0:
             raise ValueError(f"generate: prefill_chunk must be >= 0, got {prefill_chunk}")
-        _check_step(self.cfg, self.out, top_p, None, eos_token, self.pad_token, stop_check)
+        _check_step(self.cfg, self.out, top_p, None, eos_token, self.pad_token, stop_check, temperature)
         if new < 0:
             raise ValueError(f"generate: max_new_tokens must be >= 0, got {new}")
         for b in range(self.B):
             if not self._done_h[b] and self._len_h[b] + new > self.max_len:
                 raise ValueError(f"GenerationSession.generate: row {b} holds {self._len_h[b]} tokens; {new} more "
                                  f"would pass max_len={self.max_len}")
+        sp = Sampling(self.cfg.vocab_size, temperature, top_k, top_p, self.seed, self.sample0,
+                      -1 if eos_token is None else int(eos_token), self.pad_token)
+        return self.run(new, sp, int(stop_check) if eos_token is not None else 0, int(prefill_chunk))
+
+    @torch.no_grad()
+    def run(self, new: int, sp: Sampling, check: int, prefill_chunk: int):
+        """``generate`` on checked arguments (``generate()`` with ``prefill_chunk`` > 0 comes in here)."""
         self.steps = 0
         if new == 0 or all(self._done_h):
             return self.out.clone(), self.lengths.to(torch.int64)
-        eos = -1 if eos_token is None else int(eos_token)
-        check = int(stop_check) if eos_token is not None else 0
-        may_be_done = eos_token is not None or any(self._done_h)
-        was_training = [m.training for m in self.stages]
-        for m in self.stages:
-            m.eval()
-        try:
+        may_be_done = sp.eos >= 0 or any(self._done_h)
+        with eval_stages(self.stages):
             u = [0 if d else n - ch for n, ch, d in zip(self._len_h, self._cached_h, self._done_h)]
-            logits = self._catch_up(u, int(prefill_chunk), may_be_done)
+            logits = self._catch_up(u, prefill_chunk, may_be_done)
             self._fresh = False
             lens = self.caches[-1].lens  # the position of the token drawn: every live row's length
-            for t in range(new):
-                tok = sample_step(logits, self.cfg.vocab_size, temperature, top_k, top_p, self.seed, self.sample0,
-                                  lens, self.out, self.done, self.lengths, eos, self.pad_token)
-                self.steps = t + 1
-                if t + 1 == new or (check and (t + 1) % check == 0 and bool(self.done.min().item())):
-                    break
-                logits = self._decode(tok, may_be_done)
-        finally:
-            for m, tr in zip(self.stages, was_training):
-                m.train(tr)
+            self.steps = decode_loop(logits, new, check, lambda logits, t: sp.step(logits, lens, self),
+                                     lambda tok, t: self._decode(tok, may_be_done),
+                                     lambda: bool(self.done.min().item()))
         # the one read of the call: the host's bounds become exact again
         state = torch.stack([self.lengths, self.done]).tolist()
         self._len_h, self._done_h = [int(v) for v in state[0]], [bool(v) for v in state[1]]

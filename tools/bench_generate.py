@@ -56,6 +56,7 @@ from simple_distributed_machine_learning_amd.ops.decode import sample_logits, sa
 from simple_distributed_machine_learning_amd.ops.transformer import add_layer_norm, layer_norm_pass  # noqa: E402
 from simple_distributed_machine_learning_amd.parallel import PipelineEngine, init_mesh  # noqa: E402
 from simple_distributed_machine_learning_amd.parallel.decode_graph import DecodeSession  # noqa: E402
+from simple_distributed_machine_learning_amd.parallel.gen_common import Sampling  # noqa: E402
 
 DEV = torch.device("cuda", 0)
 BF = torch.bfloat16
@@ -340,7 +341,7 @@ def bench_fused_kernels(B, ctxs, rounds, reps, emit):
         del kc, vc
 
 
-SAMPLE_KW = dict(vocab=50257, temperature=0.0, top_k=0, top_p=1.0, seed=0, sample0=0, eos=-1, pad=0)
+SAMPLING = Sampling(vocab=50257, temperature=0.0, top_k=0, top_p=1.0, seed=0, sample0=0, eos=-1, pad=0)
 
 
 @torch.no_grad()
@@ -348,7 +349,7 @@ def graph_session(engine, B, ctx, steps, sites):
     """A captured step (generate(graph=True)'s session) over caches of ctx + steps rows with random contents."""
     ctx = min(ctx, engine.stages[0].cfg.block_size - steps)
     ses = DecodeSession(engine, None, B, ctx + steps, _sites=sites)
-    ses.capture(engine, SAMPLE_KW)
+    ses.capture(engine, SAMPLING)
     for c in ses.caches.values():
         for t in c.k + c.v:
             t.normal_()
