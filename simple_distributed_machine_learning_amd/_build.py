@@ -118,6 +118,13 @@ def _obj_path(cmd_base, src: Path, include_dirs, tag: str) -> Path:
 KEY_MARKER = b"SDML_BUILD_KEY="
 
 
+# Flags of single kernel files. beam.hip is compiled with the packed fp32 instructions (v_pk_add_f32, v_pk_mul_f32,
+# v_pk_fma_f32) switched off in the code generator. Today its device code is the same with and without the flag (no
+# packed instruction either way, 128 VGPRs, 8 spilled): the flag is a guard, so that no later edit or compiler makes
+# the reductions' adds packed ones; the older files keep the flags they were tuned and measured with.
+KERNEL_FILE_FLAGS = {"beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _plan(what: str):
     """(compile command, source, include dirs, tag) of every object the module ``what`` links."""
     if what == "runtime":
@@ -140,7 +147,7 @@ def _plan(what: str):
               "-Wno-unused-result", "-Wno-deprecated-declarations"] + exp
     binc = common + tinc + [_python_include(), "/opt/rocm/include"]
     bflags += [f"-I{d}" for d in binc]
-    return ([(kflags, s, common, "k") for s in sorted(kdir.glob("*.hip"))]
+    return ([(kflags + KERNEL_FILE_FLAGS.get(s.name, []), s, common, "k") for s in sorted(kdir.glob("*.hip"))]
             + [(bflags, s, binc, "b") for s in sorted(kdir.glob("*.cpp"))])
 
 

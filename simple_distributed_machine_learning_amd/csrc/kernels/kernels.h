@@ -636,6 +636,38 @@ void sample_step_bf16(const SampleStepArgs& a, hipStream_t stream);
 // out[r] = bf16(wte[tok[r]] + wpe[pos[r]])  (C % 4 == 0; wte [V][C], wpe [P][C]; pos int32 on the device)
 void embedding_at_bf16(const int64_t* tok, const int* pos, const void* wte, const void* wpe, void* out, int rows, int C,
                        int V, int P, hipStream_t stream);
+// Beam search's step on the device (beam.hip; ops/reference.py beam_step is the definition). R = B K rows, row b K + j
+// beam j of prompt b. logits [R][ld] bf16 (16-byte aligned rows, ld % 8 == 0), columns < vocab take part. score /
+// fin / glen [R]: the rows' state, only read. Two launches: the row pass leaves each row's <= K candidates in cand_tok
+// / cand_score [R][kBeamMaxK] (token -1: no candidate), the merge writes the K best per prompt to tok / par /
+// score_new / fin_new / glen_new [R] and all_done [1]. 2 <= K <= kBeamMaxK, R <= kBeamMaxRows, K <= vocab <=
+// kBeamMaxVocab (the row sits in the registers of one workgroup). No float atomics: the same bits on every run.
+constexpr int kBeamMaxK = 8;
+constexpr int kBeamMaxRows = 64;
+constexpr int kBeamMaxVocab = 65536;
+struct BeamStepArgs {
+  const void* logits = nullptr;
+  int B = 0, K = 0, ld = 0, vocab = 0;
+  const float* score = nullptr;
+  const int *fin = nullptr, *glen = nullptr;
+  int* cand_tok = nullptr;
+  float* cand_score = nullptr;
+  int64_t* tok = nullptr;
+  int* par = nullptr;
+  float* score_new = nullptr;
+  int *fin_new = nullptr, *glen_new = nullptr, *all_done = nullptr;
+  int64_t eos = -1, pad = 0;
+};
+void beam_step_bf16(const BeamStepArgs& a, hipStream_t stream);
+// dst[lk][r][0 .. copy_elems) = src[lk][(r / K) K + par[r]][0 .. copy_elems) for lk < LK, r < R: the beams' suffix
+// caches follow their parents, all layers' k and v in one launch. Rows are row_elems bf16 apart; both counts % 8 == 0,
+// 16-byte aligned bases. A par outside [0, K) copies nothing.
+void beam_gather_kv_bf16(const void* src, void* dst, const int* par, int LK, int R, int K, long row_elems,
+                         long copy_elems, hipStream_t stream);
+// out[r][plen[r] + t] for t < steps = the token of row r's hypothesis at step t, read off tok_hist / par_hist
+// [steps][R] from the last step back (pad at t >= glen[r]); columns outside [0, W) are not written.
+void beam_backtrack(const int64_t* tok_hist, const int* par_hist, const int* glen, const int64_t* plen, int64_t* out,
+                    long ld_out, int W, int R, int K, int steps, int64_t pad, hipStream_t stream);
 
 // ---- reference CNN (MNIST), fp32, one launch per stage pass (ref_cnn.hip) ------------------
 // Dropout masks: keep iff u(seed_eff, sample0 + n, unit) >= p, scale 1/(1-p) (drop == false: off),

@@ -36,27 +36,19 @@
 
 #include "dropout_hash.h"
 #include "kernels.h"
+#include "logit_key.h"  // bf2f, key16, is_nan_bf16: shared with beam.hip
 
 namespace sdml {
 namespace {
 
-typedef unsigned short u16;
 typedef u16 u16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ST = 1024;  // sampler threads per row
 
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
 __device__ __forceinline__ u16 f2bf(float f) {
   __hip_bfloat16 h = __float2bfloat16(f);
   return *reinterpret_cast<u16*>(&h);
 }
-
-// order-preserving 16-bit key of a bf16 bit pattern (larger value <-> larger key); -0 -> the key of +0
-__device__ __forceinline__ unsigned key16(u16 b) {
-  if (b == 0x8000u) b = 0;
-  return (b & 0x8000u) ? (unsigned)(u16)~b : (unsigned)b | 0x8000u;
-}
-__device__ __forceinline__ bool is_nan_bf16(u16 b) { return (b & 0x7FFFu) > 0x7F80u; }
 
 // better(a, b): does (sa, ia) beat (sb, ib)? larger score, then lower index; index < 0 = nothing yet
 __device__ __forceinline__ bool better(float sa, int ia, float sb, int ib) {

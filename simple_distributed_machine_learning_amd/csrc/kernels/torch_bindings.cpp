@@ -2484,8 +2484,117 @@ torch::Tensor embedding_at(torch::Tensor tok, torch::Tensor pos, torch::Tensor w
   return out;
 }
 
+// Beam search's step (kernels.h BeamStepArgs; ops/reference.py beam_step). logits bf16 [B K, ld]; score fp32, fin and
+// glen int32 [B K], only read. tok_out int64 / par_out int32 [B K] (a row of the call's histories) or None. Returns
+// (tok, par, score_new, fin_new, glen_new, all_done [1]), new tensors but for the two given.
+std::vector<torch::Tensor> beam_step(torch::Tensor logits, int64_t vocab, int64_t K, torch::Tensor score,
+                                     torch::Tensor fin, torch::Tensor glen, int64_t eos, int64_t pad,
+                                     c10::optional<torch::Tensor> tok_out, c10::optional<torch::Tensor> par_out) {
+  TORCH_CHECK(K >= 2 && K <= sdml::kBeamMaxK, "beam_step: K = ", K, " beams, 2..", sdml::kBeamMaxK, " are supported");
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kBFloat16 && logits.dim() == 2 &&
+                  logits.stride(1) == 1 && (logits.size(0) <= 1 || logits.stride(0) >= logits.size(1)),
+              "beam_step: logits must be a [B K, ld] bf16 device tensor with unit column stride");
+  const int64_t R = logits.size(0), ld = R > 1 ? logits.stride(0) : logits.size(1);
+  TORCH_CHECK(R >= K && R % K == 0 && R <= sdml::kBeamMaxRows, "beam_step: ", R, " rows, a multiple of K = ", K,
+              " up to ", sdml::kBeamMaxRows, " is supported");
+  TORCH_CHECK(vocab >= K && vocab <= logits.size(1) && vocab <= sdml::kBeamMaxVocab, "beam_step: vocab ", vocab,
+              " outside ", K, "..min(", logits.size(1), " columns, ", sdml::kBeamMaxVocab, ")");
+  TORCH_CHECK(ld % 8 == 0 && logits.size(1) % 8 == 0 && aligned16(logits),
+              "beam_step: the logits' rows must be 16-byte aligned and a multiple of 8 columns wide");
+  TORCH_CHECK(eos >= -1 && eos < vocab && pad >= 0 && pad < vocab, "beam_step: eos / pad outside the vocabulary");
+  TORCH_CHECK(score.is_cuda() && score.device() == logits.device() && score.scalar_type() == torch::kFloat32 &&
+                  score.is_contiguous() && score.numel() == R,
+              "beam_step: score must be a contiguous fp32 [B K] device tensor");
+  for (const auto* t : {&fin, &glen})
+    TORCH_CHECK(t->is_cuda() && t->device() == logits.device() && t->scalar_type() == torch::kInt32 &&
+                    t->is_contiguous() && t->numel() == R,
+                "beam_step: fin and glen must be contiguous int32 [B K] device tensors");
+  auto given = [&](const c10::optional<torch::Tensor>& t, torch::ScalarType ty, const char* what) {
+    if (!t.has_value() || !t->defined()) return torch::empty({R}, logits.options().dtype(ty));
+    TORCH_CHECK(t->is_cuda() && t->device() == logits.device() && t->scalar_type() == ty && t->is_contiguous() &&
+                    t->numel() == R,
+                "beam_step: ", what, " must be a contiguous [B K] device tensor of its type");
+    return *t;
+  };
+  auto tok = given(tok_out, torch::kInt64, "tok_out (int64)");
+  auto par = given(par_out, torch::kInt32, "par_out (int32)");
+  // one allocation per type: the candidates of the row pass, then the new state
+  auto fbuf = torch::empty({R * (sdml::kBeamMaxK + 1)}, score.options());
+  auto ibuf = torch::empty({R * (sdml::kBeamMaxK + 2) + 1}, fin.options());
+  const int64_t c = R * sdml::kBeamMaxK;
+  auto score_new = fbuf.narrow(0, c, R), fin_new = ibuf.narrow(0, c, R), glen_new = ibuf.narrow(0, c + R, R);
+  auto all_done = ibuf.narrow(0, c + 2 * R, 1);
+  sdml::BeamStepArgs a;
+  a.logits = logits.data_ptr();
+  a.B = (int)(R / K), a.K = (int)K, a.ld = (int)ld, a.vocab = (int)vocab;
+  a.score = score.data_ptr<float>(), a.fin = fin.data_ptr<int>(), a.glen = glen.data_ptr<int>();
+  a.cand_tok = ibuf.data_ptr<int>(), a.cand_score = fbuf.data_ptr<float>();
+  a.tok = tok.data_ptr<int64_t>(), a.par = par.data_ptr<int>();
+  a.score_new = score_new.data_ptr<float>();
+  a.fin_new = fin_new.data_ptr<int>(), a.glen_new = glen_new.data_ptr<int>(), a.all_done = all_done.data_ptr<int>();
+  a.eos = eos, a.pad = pad;
+  sdml::beam_step_bf16(a, cur_stream());
+  return {tok, par, score_new, fin_new, glen_new, all_done};
+}
+
+// The beams' suffix caches follow their parents: buf bf16 [2, L, 2, R, nmax, H, D] contiguous; positions < u of
+// buf[1 - half][l][kv][r] become those of buf[half][l][kv][(r / K) K + par[r]]. par int32 [R] on the device.
+void beam_gather_kv(torch::Tensor buf, int64_t half, torch::Tensor par, int64_t K, int64_t u) {
+  TORCH_CHECK(buf.is_cuda() && buf.scalar_type() == torch::kBFloat16 && buf.is_contiguous() && buf.dim() == 7 &&
+                  buf.size(0) == 2 && buf.size(2) == 2,
+              "beam_gather_kv: buf must be a contiguous bf16 [2, L, 2, R, nmax, H, D] device tensor");
+  const int64_t L = buf.size(1), R = buf.size(3), nmax = buf.size(4), HD = buf.size(5) * buf.size(6);
+  TORCH_CHECK(half == 0 || half == 1, "beam_gather_kv: half must be 0 or 1");
+  TORCH_CHECK(K >= 1 && R % K == 0 && u >= 0 && u <= nmax, "beam_gather_kv: R = ", R, " rows in groups of K = ", K,
+              ", u = ", u, " of nmax = ", nmax, " positions");
+  TORCH_CHECK(HD % 8 == 0 && aligned16(buf) && L * 2 <= 65535 && R <= 65535,
+              "beam_gather_kv: H D must be a multiple of 8 (16-byte copies) and the storage 16-byte aligned");
+  TORCH_CHECK(par.is_cuda() && par.device() == buf.device() && par.scalar_type() == torch::kInt32 &&
+                  par.is_contiguous() && par.numel() == R,
+              "beam_gather_kv: par must be a contiguous int32 [R] tensor on buf's device");
+  const auto* base = static_cast<const char*>(buf.data_ptr());
+  const int64_t half_bytes = buf.stride(0) * 2;
+  sdml::beam_gather_kv_bf16(base + half * half_bytes, const_cast<char*>(base) + (1 - half) * half_bytes,
+                            par.data_ptr<int>(), (int)(L * 2), (int)R, (int)K, (long)(nmax * HD), (long)(u * HD),
+                            cur_stream());
+}
+
+// out int64 [R, W] gets row r's hypothesis at columns plen[r] + t, t < steps, traced back through tok_hist int64 /
+// par_hist int32 [>= steps, R]; pad at t >= glen[r]. plen int64 [R], glen int32 [R].
+void beam_backtrack(torch::Tensor out, torch::Tensor plen, torch::Tensor tok_hist, torch::Tensor par_hist,
+                    torch::Tensor glen, int64_t steps, int64_t K, int64_t pad) {
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kInt64 && out.dim() == 2 && out.size(1) >= 1 &&
+                  out.size(1) <= INT_MAX && out.stride(1) == 1 && (out.size(0) <= 1 || out.stride(0) >= out.size(1)),
+              "beam_backtrack: out must be an int64 [R, W] device tensor with unit column stride");
+  const int64_t R = out.size(0);
+  TORCH_CHECK(K >= 1 && R >= 1 && R % K == 0 && R <= INT_MAX, "beam_backtrack: R = ", R, " rows in groups of K = ", K);
+  TORCH_CHECK(tok_hist.is_cuda() && tok_hist.scalar_type() == torch::kInt64 && tok_hist.is_contiguous() &&
+                  par_hist.is_cuda() && par_hist.scalar_type() == torch::kInt32 && par_hist.is_contiguous() &&
+                  tok_hist.dim() == 2 && par_hist.dim() == 2 && tok_hist.size(1) == R && par_hist.size(1) == R &&
+                  steps >= 0 && steps <= tok_hist.size(0) && steps <= par_hist.size(0) && steps <= INT_MAX,
+              "beam_backtrack: tok_hist int64 / par_hist int32 must be contiguous [>= steps, R] device tensors");
+  TORCH_CHECK(glen.is_cuda() && glen.scalar_type() == torch::kInt32 && glen.is_contiguous() && glen.numel() == R &&
+                  plen.is_cuda() && plen.scalar_type() == torch::kInt64 && plen.is_contiguous() && plen.numel() == R,
+              "beam_backtrack: glen int32 / plen int64 must be contiguous [R] device tensors");
+  for (const auto* t : {&plen, &tok_hist, &par_hist, &glen})
+    TORCH_CHECK(t->device() == out.device(), "beam_backtrack: all tensors must be on one device");
+  sdml::beam_backtrack(tok_hist.data_ptr<int64_t>(), par_hist.data_ptr<int>(), glen.data_ptr<int>(),
+                       plen.data_ptr<int64_t>(), out.data_ptr<int64_t>(),
+                       R > 1 ? (long)out.stride(0) : (long)out.size(1), (int)out.size(1), (int)R, (int)K, (int)steps,
+                       pad, cur_stream());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "sdml gfx950 HIP kernels";
+  m.def("beam_step", &beam_step,
+        "beam search's step: each row's K best continuations, then the K best of a prompt's K K (two launches)",
+        py::arg("logits"), py::arg("vocab"), py::arg("K"), py::arg("score"), py::arg("fin"), py::arg("glen"),
+        py::arg("eos") = -1, py::arg("pad") = 0, py::arg("tok_out") = py::none(), py::arg("par_out") = py::none());
+  m.def("beam_gather_kv", &beam_gather_kv, "re-parent the beams' suffix caches, every layer's k and v in one launch",
+        py::arg("buf"), py::arg("half"), py::arg("par"), py::arg("K"), py::arg("u"));
+  m.def("beam_backtrack", &beam_backtrack, "trace the beams' tokens back through the parents into the token matrix",
+        py::arg("out"), py::arg("plen"), py::arg("tok_hist"), py::arg("par_hist"), py::arg("glen"), py::arg("steps"),
+        py::arg("K"), py::arg("pad"));
   m.def("attention_decode", &attention_decode,
         "one new token per sample against a KV cache (bf16, d=64): writes k, v at row lens[b], returns [B, C]",
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("n_keys"),

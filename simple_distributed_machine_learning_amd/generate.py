@@ -88,6 +88,13 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--num_samples", type=int, default=1, metavar="N",
                    help="N continuations of every prompt from one prefill and one copy of the prompt's keys (1..64; "
                         "above 1: one rank, not with --graph, --lookup or --prefill_chunk)")
+    s.add_argument("--num_beams", type=int, default=1, metavar="K",
+                   help="beam search with K hypotheses per prompt (1..8; above 1: greedy arguments only, one rank, not "
+                        "with --num_samples, --graph, --lookup or --prefill_chunk); prints the best one per prompt")
+    s.add_argument("--length_penalty", type=float, default=0.0,
+                   help="with --num_beams: rank a prompt's hypotheses by score / length ** this (0: the raw score)")
+    s.add_argument("--return_beams", action="store_true",
+                   help="with --num_beams: print all K hypotheses of every prompt, best first")
     return p
 
 
@@ -160,18 +167,22 @@ def run(args) -> dict:
                        top_k=args.top_k, seed=args.seed, top_p=args.top_p, prompt_lens=plens,
                        eos_token=args.eos_token, pad_token=args.pad_token, stop_check=args.stop_check,
                        return_lengths=True, graph=args.graph, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
-                       return_stats=not args.graph, prefill_chunk=args.prefill_chunk, num_samples=args.num_samples)
+                       return_stats=not args.graph, prefill_chunk=args.prefill_chunk, num_samples=args.num_samples,
+                       num_beams=args.num_beams, length_penalty=args.length_penalty,
+                       return_beams=args.return_beams and args.num_beams > 1)
         out, lengths = res[0], res[1]
-        steps = res[2]["steps"] if len(res) > 2 else None
+        steps = res[2]["steps"] if len(res) > 2 and isinstance(res[2], dict) else None
         rows = out.cpu().tolist()  # (the read-back ends the timed region)
         lengths = lengths.cpu().tolist()
         dt_s = time.perf_counter() - t0
     except ValueError as e:  # the refusals (tp, dp, rotate, lengths): their message, not a traceback
         shutdown(mesh)
         raise SystemExit(str(e))
-    if plens is not None or args.eos_token is not None or args.lookup:  # each row up to its own length
+    beams = args.num_beams > 1
+    if plens is not None or args.eos_token is not None or args.lookup or beams:  # each row up to its own length
         rows = [r[:n] for r, n in zip(rows, lengths)]
-    n_prompt = len(rows) * prompts.shape[1] if plens is None else int(plens.sum()) * args.num_samples
+    n_prompt = len(rows) * prompts.shape[1] if plens is None else int(plens.sum()) * args.num_samples * \
+        (args.num_beams if beams and args.return_beams else 1)
     n_new = sum(lengths) - n_prompt  # the tokens really generated (the eos included), over all rows
     if mesh.is_master():
         for r in rows:
@@ -180,7 +191,7 @@ def run(args) -> dict:
                     tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k,
                     top_p=args.top_p, graph=bool(args.graph), lookup=args.lookup, lookup_ngram=args.lookup_ngram,
                     steps=steps, tokens_per_step=None if not steps else n_new / steps,
-                    num_samples=args.num_samples)
+                    num_samples=args.num_samples, num_beams=args.num_beams)
     return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
 
 

@@ -29,8 +29,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .base import ModelSpec, PipelineStage
-from ..ops.decode import (ATTENTION_APPEND_MAX_T, ATTENTION_FORK_MAX_N, LINEAR_DECODE_MAX_M, attention_append,
-                          attention_decode, attention_extend, attention_fork, embedding_at, linear_decode)
+from ..ops.decode import (ATTENTION_APPEND_MAX_T, ATTENTION_FORK_MAX_N, BEAM_MAX_K, LINEAR_DECODE_MAX_M,
+                          attention_append, attention_decode, attention_extend, attention_fork, beam_gather_kv,
+                          embedding_at, linear_decode)
 from ..ops.linear import Linear, _w_padded, linear, lm_head, mlp_gelu
 from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
                              dropout_threshold)
@@ -477,11 +478,11 @@ class GPT2Stage(PipelineStage):
         cache.n += 1
         return self._head_logits(self._normed(x, y)) if self.is_last else x
 
-    def fork_cache(self, cache: "KVCache", n_samples: int, nmax: int) -> "ForkedKVCache":
+    def fork_cache(self, cache: "KVCache", n_samples: int, nmax: int, suffix=None) -> "ForkedKVCache":
         """n_samples continuations of every prompt of a prefilled ``cache``: the cache itself becomes the shared
         prefix (its ``lens`` are the prompt lengths; it is only read from here on), and every row b n + j, sibling j
         of prompt b, gets ``nmax`` suffix positions of its own per local layer. ``cache.n + nmax`` may not exceed
-        block_size."""
+        block_size. ``suffix`` = (ks, vs): the caller's storage for the suffixes (``beam_cache``), not new tensors."""
         if isinstance(n_samples, bool) or not isinstance(n_samples, int) or not 1 <= n_samples <= ATTENTION_FORK_MAX_N:
             raise ValueError(f"fork_cache: n_samples must be an integer in 1..{ATTENTION_FORK_MAX_N}, got {n_samples!r}")
         if cache.n < 1:
@@ -490,9 +491,24 @@ class GPT2Stage(PipelineStage):
             raise ValueError(f"fork_cache: {cache.n} prompt positions + nmax = {nmax} must lie in {cache.n + 1}.."
                              f"block_size={self.cfg.block_size}")
         R = cache.lens.shape[0] * n_samples
-        mk = lambda t: torch.empty((R, nmax) + t.shape[2:], dtype=t.dtype, device=t.device)  # noqa: E731
-        return ForkedKVCache(cache, [mk(t) for t in cache.k], [mk(t) for t in cache.v],
-                             cache.lens.repeat_interleave(n_samples), n_samples, cache.n, int(nmax))
+        if suffix is None:
+            mk = lambda t: torch.empty((R, nmax) + t.shape[2:], dtype=t.dtype, device=t.device)  # noqa: E731
+            suffix = [mk(t) for t in cache.k], [mk(t) for t in cache.v]
+        return ForkedKVCache(cache, *suffix, cache.lens.repeat_interleave(n_samples), n_samples, cache.n, int(nmax))
+
+    def beam_cache(self, cache: "KVCache", K: int, nmax: int) -> "BeamKVCache":
+        """``fork_cache`` for the K beams of every prompt (``generate(num_beams=K)``), with suffixes that can follow
+        their parents: all local layers' k and v suffixes live twice in one allocation [2, L, 2, B K, nmax, H, D],
+        ``ks`` / ``vs`` are views into the current half, and ``reparent(par)`` copies row (b, par[r])'s positions in
+        use into row r of the other half in one launch (ops/decode.py beam_gather_kv) and makes that half current.
+        ``decode_step_forked`` takes the result as it takes a forked cache."""
+        if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= BEAM_MAX_K:
+            raise ValueError(f"beam_cache: K must be an integer in 2..{BEAM_MAX_K}, got {K!r}")
+        p = next(self.parameters())
+        H, D = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        buf = torch.empty((2, len(self.h), 2, cache.lens.shape[0] * K, int(nmax), H, D), dtype=p.dtype, device=p.device)
+        fc = self.fork_cache(cache, K, nmax, suffix=(list(buf[0, :, 0]), list(buf[0, :, 1])))
+        return BeamKVCache(fc.prefix, fc.ks, fc.vs, fc.lens, K, fc.n, fc.nmax, buf)
 
     @torch.no_grad()
     def decode_step_forked(self, x, fc: "ForkedKVCache"):
@@ -609,6 +625,22 @@ class ForkedKVCache:
     n_samples: int
     n: int
     nmax: int
+
+
+@dataclass
+class BeamKVCache(ForkedKVCache):
+    """A forked cache whose K rows per prompt are beams (``GPT2Stage.beam_cache``): ``buf`` [2, L, 2, B K, nmax, H, D]
+    holds every local layer's k and v suffixes twice, ``ks`` / ``vs`` are views into half ``half``."""
+    buf: torch.Tensor = None
+    half: int = 0
+
+    def reparent(self, par):
+        """Row r continues beam par[r] (int32 [B K] on the device, the parent's index inside its prompt): the suffix
+        positions in use move from the parents' rows of the current half to the rows of the other, which becomes
+        current. One launch for all local layers; nothing is read back."""
+        beam_gather_kv(self.buf, self.half, par, self.n_samples, self.n - self.prefix.n)
+        self.half = 1 - self.half
+        self.ks, self.vs = list(self.buf[self.half, :, 0]), list(self.buf[self.half, :, 1])
 
 
 def gpt2_spec(num_stages: int = 2, cfg: GPT2Config = None, seq_len: int = None, dtype=torch.bfloat16,

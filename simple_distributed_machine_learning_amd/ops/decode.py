@@ -1,5 +1,5 @@
 """Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, attention_append.hip,
-attention_extend.hip, attention_fork.hip, linear_decode.hip, sample.hip, lookup.hip) and their torch twins.
+attention_extend.hip, attention_fork.hip, linear_decode.hip, sample.hip, lookup.hip, beam.hip) and their torch twins.
 
 Dispatch: ROCm bf16 tensors (head width 64 for the attention) run the hand-written kernels, and a shape the kernels do
 not take is an error there, never a library call. CPU tensors, fp32 and other head widths run the twins below, which
@@ -20,6 +20,8 @@ LINEAR_DECODE_MAX_M = 64  # kLinearDecodeMaxM
 ATTENTION_APPEND_MAX_T = 8  # kAttnAppendMaxT
 ATTENTION_FORK_MAX_N = 64  # kAttnForkMaxN
 LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM = 7, 8  # kLookupMaxDrafts, kLookupMaxNgram
+BEAM_MAX_K, BEAM_MAX_ROWS, BEAM_MAX_VOCAB = 8, 64, 65536  # kBeamMaxK, kBeamMaxRows, kBeamMaxVocab
+BEAM_THREADS = 1024  # beam.hip's threads per logits row
 
 
 def _hip_bf16(*ts) -> bool:
@@ -294,6 +296,80 @@ def lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, k:
                                            int(ngram), int(eos), int(pad)))
     return _ref.lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, int(k), int(ngram), int(eos),
                             int(pad))
+
+
+def _beam_kernel_error(e: RuntimeError, who: str):
+    """A binding's refusal (its message names the op) leaves as ValueError, like the twin path's; else re-raise."""
+    if not str(e).startswith(who + ":"):
+        raise e
+    raise ValueError(str(e).split("\n")[0]) from None
+
+
+def beam_step(logits, vocab: int, K: int, score, fin, glen, eos: int = -1, pad: int = 0, tok_out=None, par_out=None):
+    """One step of beam search over R = B K rows (ops/reference.py beam_step is the definition): every live row's K
+    best continuations with their cumulative scores, then the K best per prompt. Returns (tok int64, par int32,
+    score_new fp32, fin_new int32, glen_new int32, all [R], all_done int32 [1]); the inputs are not changed, so the
+    state is double-buffered. ``tok_out`` / ``par_out`` [R]: rows of the caller's histories to write tok / par into.
+    ROCm bf16: beam.hip, two launches and no host synchronisation, for 2 <= K <= 8, R <= 64, vocab <= 65536."""
+    if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= BEAM_MAX_K:
+        raise ValueError(f"beam_step: K must be an integer in 2..{BEAM_MAX_K} (beams per prompt), got {K!r}")
+    R = logits.shape[0] if logits.dim() == 2 else 0
+    if R < K or R % K or not K <= int(vocab) <= logits.shape[1]:
+        raise ValueError(f"beam_step: logits must be [B K, ld >= vocab >= K], got {tuple(logits.shape)}, K={K}, "
+                         f"vocab={vocab}")
+    for name, t, dt in (("score", score, torch.float32), ("fin", fin, torch.int32), ("glen", glen, torch.int32)):
+        if t.dtype != dt or t.shape != (R,):
+            raise ValueError(f"beam_step: {name} must be {dt} [{R}], got {t.dtype} {tuple(t.shape)}")
+    if _hip_bf16(logits):
+        try:
+            return tuple(kernels().beam_step(logits, int(vocab), K, score, fin, glen, int(eos), int(pad), tok_out,
+                                             par_out))
+        except RuntimeError as e:
+            _beam_kernel_error(e, "beam_step")
+    return _ref.beam_step(logits, int(vocab), K, score, fin, glen, int(eos), int(pad), tok_out, par_out)
+
+
+def beam_gather_kv(buf, half: int, par, K: int, u: int):
+    """Re-parent the beams' suffix caches: ``buf`` [2, L, 2, R, nmax, H, D], both halves of the ping-pong for all local
+    layers' k and v; positions < u of buf[1 - half][l, kv, r] become those of buf[half][l, kv, (r // K) K + par[r]]
+    (``par`` int32 [R] on the device). ROCm bf16: one launch of beam.hip's gather."""
+    if buf.dim() != 7 or buf.shape[0] != 2 or buf.shape[2] != 2 or half not in (0, 1) or buf.shape[3] % int(K) or \
+            not 0 <= int(u) <= buf.shape[4] or par.dtype != torch.int32 or par.shape != (buf.shape[3],):
+        raise ValueError(f"beam_gather_kv: buf must be [2, L, 2, R, nmax, H, D] with R a multiple of K, half 0 or 1, "
+                         f"u in 0..nmax and par int32 [R], got {tuple(buf.shape)}, half={half}, K={K}, u={u}, "
+                         f"{par.dtype} {tuple(par.shape)}")
+    if buf.shape[1] == 0 or int(u) == 0:
+        return
+    if _hip_bf16(buf):
+        try:
+            return kernels().beam_gather_kv(buf, int(half), par, int(K), int(u))
+        except RuntimeError as e:
+            _beam_kernel_error(e, "beam_gather_kv")
+    return _ref.beam_gather_kv(buf, int(half), par, int(K), int(u))
+
+
+def beam_backtrack(out, plen, tok_hist, par_hist, glen, steps: int, K: int, pad: int = 0):
+    """Write every row's hypothesis into the token matrix: out[r, plen[r] + t], t < steps, traced back through
+    ``tok_hist`` int64 / ``par_hist`` int32 [>= steps, R]; ``pad`` at t >= glen[r]. Device tensors: one launch."""
+    if out.is_cuda:
+        try:
+            return kernels().beam_backtrack(out, plen, tok_hist, par_hist, glen, int(steps), int(K), int(pad))
+        except RuntimeError as e:
+            _beam_kernel_error(e, "beam_backtrack")
+    return _ref.beam_backtrack(out, plen, tok_hist, par_hist, glen, int(steps), int(K), int(pad))
+
+
+def beam_score_budget(vocab: int, lse: float, score: float, logp: float, threads: int = BEAM_THREADS) -> float:
+    """The bound E on |c - exact| of one candidate score c = score + (z - lse) of beam.hip's row pass (and of the fp32
+    twin summing in any order no deeper), derived in docs/NUMERICS.md "Beam step": ``lse`` the row's log-sum-exp,
+    ``score`` the row's cumulative score, ``logp`` = z - lse, the three as magnitudes of the exact values."""
+    u = 2.0 ** -24  # fp32 unit roundoff; a library function good to 2 ulp has a relative error of 4 u
+    pieces = (int(vocab) + 7) // 8  # 16-byte pieces of 8 logits, dealt round-robin to the threads
+    per_thread = 8 * ((pieces + threads - 1) // threads)  # logits a thread sums
+    depth = per_thread + 6 + threads // 64  # adds on the longest path: the thread's, the wave's 6, the wave sums'
+    d_sum = (depth + 4 + 2 * math.log(max(int(vocab), 3))) * u  # relative error of S: adds, exp, rounded z - m
+    d_lse = d_sum + 4 * u * math.log(max(int(vocab), 3)) + u * abs(lse)  # + the log, + the rounding of m + log S
+    return 1.01 * (d_lse + u * abs(logp) + u * (abs(score) + abs(logp)))  # + z - lse, + score + (z - lse)
 
 
 def embedding_at(tok, pos, wte, wpe):

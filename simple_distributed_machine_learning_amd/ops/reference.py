@@ -498,3 +498,78 @@ def lookup_step(g, tok_in, nq_in, out, lens, limit, done, gen_len, row_steps, k:
         nq_next[b] = 1 + n
     all_done = (nq_next.max() == 0).to(torch.int32).reshape(1)
     return tok_next, nq_next, all_done
+
+
+# ---- generation: beam search (csrc/kernels/beam.hip) -----------------------------------------------------------------
+def beam_step(logits, vocab: int, K: int, score, fin, glen, eos: int = -1, pad: int = 0, tok_out=None, par_out=None):
+    """One step of beam search over R = B K rows, row b K + j beam j of prompt b; the definition of beam.hip's step.
+
+    ``logits`` [R, ld], columns < ``vocab`` taking part; a NaN counts as -inf in m and lse and is never a candidate
+    (a row with fewer than K logits that are no NaN has that many candidates); ``score`` fp32, ``fin`` and ``glen``
+    int32 [R]: the rows' cumulative log-probability, finished flag and generated length. None of them is changed.
+
+    A live row's candidates are its K tokens that rank highest by (logit descending, token id ascending), candidate
+    i with c = score[r] + (float(z_v) - lse), one fp32 subtract and then one fp32 add, lse = m + log(sum_v exp(z_v -
+    m)) in fp32, m = max_v z_v (a logit of -inf: c = -inf). A finished row has one candidate, (``pad``, score[r]).
+    Per prompt the K best of the <= K K candidates by (c descending, parent j ascending, rank-in-row ascending), a c
+    of -inf losing to every finite one, become the new rows: output j takes the j-th best, ``fin_new`` = the
+    parent's flag or tok == ``eos``, ``glen_new`` = the parent's length, plus one where the parent was live.
+
+    Returns (tok int64, par int32: the parent's j, score_new fp32, fin_new int32, glen_new int32, all [R], and
+    all_done int32 [1]: every row of every prompt finished). ``tok_out`` / ``par_out``: write tok and par there."""
+    R = logits.shape[0]
+    B = R // K
+    dev = logits.device
+    z = logits[:, :vocab].float()
+    nan = torch.isnan(z)
+    z = torch.where(nan, torch.full_like(z, -math.inf), z)
+    m = z.max(dim=1).values
+    m0 = torch.where(m > -math.inf, m, torch.zeros_like(m))
+    lse = m0 + torch.log(torch.exp(z - m0[:, None]).sum(dim=1))
+    zs, ids = torch.sort(z, dim=1, descending=True, stable=True)  # (stable: ties keep the lower token id first)
+    last = torch.sort(nan.gather(1, ids).to(torch.int8), dim=1, stable=True).indices  # the NaNs behind every -inf
+    zs, ids = zs.gather(1, last)[:, :K], ids.gather(1, last)[:, :K]
+    dead = nan.gather(1, ids)  # [R, K]: slots a row with fewer than K logits that are no NaN cannot fill
+    c = score[:, None] + (zs - lse[:, None])
+    c = torch.where((zs == -math.inf) | torch.isnan(c), torch.full_like(c, -math.inf), c)
+    done = fin.bool()
+    first = torch.arange(K, device=dev)[None, :] == 0
+    c = torch.where(done[:, None], torch.where(first, score[:, None].expand(R, K), torch.full_like(c, -math.inf)), c)
+    ids = torch.where(done[:, None], torch.full_like(ids, int(pad)), ids)
+    invalid = torch.where(done[:, None], ~first, dead).view(B, K * K)
+    # candidates in (parent, rank-in-row) order; stable sorts: by c, then the slots that hold no candidate last
+    o1 = torch.sort(c.view(B, K * K), dim=1, descending=True, stable=True).indices
+    o2 = torch.sort(invalid.gather(1, o1).to(torch.int8), dim=1, stable=True).indices
+    pick = o1.gather(1, o2)[:, :K]  # [B, K] indices j K + i
+    par = (pick // K).reshape(R)
+    prow = (torch.arange(B, device=dev)[:, None] * K + pick // K).reshape(R)
+    tok = ids.reshape(B, K * K).gather(1, pick).reshape(R)
+    score_new = c.view(B, K * K).gather(1, pick).reshape(R)
+    pf = done[prow]
+    fin_new = (pf | (tok == int(eos))).to(torch.int32)
+    glen_new = glen[prow] + (~pf).to(torch.int32)
+    if tok_out is not None:
+        tok = tok_out.copy_(tok)
+    par = par.to(torch.int32) if par_out is None else par_out.copy_(par)
+    return tok, par, score_new, fin_new, glen_new, fin_new.min().reshape(1)
+
+
+def beam_gather_kv(buf, half: int, par, K: int, u: int):
+    """The beams' suffix caches follow their parents. ``buf`` [2, L, 2, R, nmax, H, D] holds both halves of the
+    ping-pong: positions < u of buf[1 - half][l, kv, r] become those of buf[half][l, kv, (r // K) K + par[r]]."""
+    R = buf.shape[3]
+    rows = torch.arange(R, device=buf.device) // K * K + par.to(torch.int64)
+    buf[1 - half][:, :, :, :u] = buf[half].index_select(2, rows)[:, :, :, :u]
+
+
+def beam_backtrack(out, plen, tok_hist, par_hist, glen, steps: int, K: int, pad: int = 0):
+    """out[r, plen[r] + t], t < steps = the token of row r's hypothesis at step t: read off ``tok_hist`` int64 /
+    ``par_hist`` int32 [>= steps, R] from the last step back to the first, ``pad`` at t >= glen[r]."""
+    R = out.shape[0]
+    rows = torch.arange(R, device=out.device)
+    base = rows // K * K
+    j = rows - base
+    for t in range(steps - 1, -1, -1):
+        tok = tok_hist[t][base + j]
+        out[rows, plen + t] = torch.where(glen > t, tok, torch.full_like(tok, int(pad)))
+        j = par_hist[t][base + j].to(torch.int64)

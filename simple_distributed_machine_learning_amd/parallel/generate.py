@@ -47,6 +47,22 @@ for its n siblings. Row ``b n + j`` is the sampler's sample ``sample0 + b n + j`
 tokens, lengths and stats are those of the call on ``prompts.repeat_interleave(n, 0)`` bit for bit (docs/NUMERICS.md).
 It is refused with ``graph=True``, ``lookup > 0``, ``prefill_chunk > 0`` and pp > 1.
 
+``num_beams=K`` (2..8, one rank) is beam search: K hypotheses per prompt, every step keeping the K continuations with
+the highest cumulative log-probability (``beam_step``, ops/reference.py: the rule, its tie-breaks included). The
+prompts are prefilled once and every stage's cache forked as for ``num_samples`` (models/gpt2.py ``beam_cache``); a
+step is the beam step, the re-parenting of every stage's suffix caches by the step's parents (one gather launch per
+stage) and ``decode_step_forked`` on the step's tokens. A hypothesis that draws the eos is finished: it keeps its
+score, rides along fed with the pad token and competes with the live ones for its place. The loop ends after
+``max_new_tokens`` steps, or at a ``stop_check`` step on which every hypothesis of every prompt is finished (the one
+flag the host reads); there is no other early-termination heuristic, so a finished hypothesis can still be displaced
+by a live one that overtakes it. At the end the tokens are traced back through the parents and a prompt's hypotheses
+ranked by ``score / length ** length_penalty`` (length = generated tokens, the eos included; 0.0: the raw score),
+lowest beam first on ties. The result is the best hypothesis per prompt, ``[B, S0 + max_new_tokens]``, or with
+``return_beams=True`` all ``[B K, ...]`` rows, best first per prompt, followed by their scores (fp32 [B K], the
+cumulative log-probabilities). It is refused with sampling (``temperature > 0``, ``top_k > 0``, ``top_p`` in (0, 1)),
+``num_samples > 1``, ``graph=True``, ``lookup > 0``, ``prefill_chunk > 0`` and pp > 1; on the kernels B K may not
+exceed 64 rows (the decode projections' bound) and the vocabulary 65536.
+
 Limitations: tensor parallelism, data parallelism and ``--schedule rotate`` are refused. With pp ranks one rank works
 at a time (a token must leave the last stage before stage 0 can embed it); several sample groups in flight would fill
 the bubble and are not implemented. ``graph=True`` is refused with pp > 1: the step's boundaries cross ranks between
@@ -55,8 +71,9 @@ verify step is not captured yet) and with pp > 1 (the other ranks' caches would 
 kernels B * (K + 1) may not exceed 64 rows.
 
 ``generate()`` itself checks the arguments and hands the call to one driver: ``_generate_pipeline`` (the plain loop),
-``_generate_lookup``, ``_generate_forked``, ``_generate_chunked`` or decode_graph's ``generate_graphed``. The token
-state, the sampling arguments, the decode loop and the form of the result are one copy, parallel/gen_common.py.
+``_generate_lookup``, ``_generate_forked``, ``_generate_beam``, ``_generate_chunked`` or decode_graph's
+``generate_graphed``. The token state, the sampling arguments, the decode loop and the form of the result are one copy,
+parallel/gen_common.py.
 """
 from __future__ import annotations
 
@@ -65,7 +82,8 @@ from typing import Optional
 
 import torch
 
-from ..ops.decode import ATTENTION_FORK_MAX_N, LINEAR_DECODE_MAX_M, LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, lookup_step
+from ..ops.decode import (ATTENTION_FORK_MAX_N, BEAM_MAX_K, BEAM_MAX_ROWS, BEAM_MAX_VOCAB, LINEAR_DECODE_MAX_M,
+                          LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, beam_backtrack, beam_step, lookup_step)
 from .decode_graph import check_graph, generate_graphed
 from .gen_common import Sampling, TokenState, decode_loop, eval_stages, result
 from .session import GenerationSession
@@ -212,6 +230,76 @@ def _generate_forked(engine, st: TokenState, sp: Sampling, new: int, check: int,
     return st.out, st.lengths(), st.lens0, steps
 
 
+def _check_beams(engine, cfg, B: int, num_beams, temperature, top_k, top_p, num_samples, graph: bool,
+                 lookup: int, prefill_chunk: int):
+    """The refusals of ``num_beams``."""
+    if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= BEAM_MAX_K:
+        raise ValueError(f"generate: num_beams must be an integer in 1..{BEAM_MAX_K}, got {num_beams!r}")
+    if num_beams == 1:
+        return
+    for on, what in ((temperature > 0, "temperature > 0 (beam search does not sample)"),
+                     (top_k > 0, "top_k > 0 (beam search does not sample)"),
+                     (0.0 < float(top_p) < 1.0, "top_p in (0, 1) (beam search does not sample)"),
+                     (num_samples > 1, "num_samples > 1 (the beams are the rows of the fork)"),
+                     (graph, "graph=True (the beam step is not captured yet)"),
+                     (lookup > 0, "lookup > 0 (the verify step does not read a shared prefix yet)"),
+                     (prefill_chunk > 0, "prefill_chunk > 0 (a session cannot be forked yet)"),
+                     (engine.mesh.pp > 1, f"pp={engine.mesh.pp} (the fork does not cross pipeline ranks yet); run one "
+                                          "rank")):
+        if on:
+            raise ValueError(f"generate: num_beams > 1 is not supported with {what}")
+    if engine.device.type == "cuda" and engine.dtype == torch.bfloat16:
+        if B * num_beams > BEAM_MAX_ROWS:
+            raise ValueError(f"generate: {B} prompts x num_beams = {num_beams} = {B * num_beams} rows per step, but "
+                             f"the beam step and the decode projections take at most {BEAM_MAX_ROWS}")
+        if cfg.vocab_size > BEAM_MAX_VOCAB:
+            raise ValueError(f"generate: num_beams > 1 takes a vocabulary of at most {BEAM_MAX_VOCAB}, got "
+                             f"{cfg.vocab_size}")
+
+
+def _generate_beam(engine, st: TokenState, sp: Sampling, new: int, check: int, K: int, length_penalty: float):
+    """The driver of ``num_beams`` = K > 1 (one rank; module docstring). ``st`` holds the B K rows of the call on
+    ``prompts.repeat_interleave(K, 0)``; row b K + j is beam j of prompt b until the final ranking. Returns the rows
+    best first per prompt, their lengths and prompt lengths, the steps and the scores."""
+    P, dev = engine.P, engine.device
+    stages = [engine.stages[s] for s in range(P)]
+    B = st.prompts.shape[0]
+    R = B * K
+    score = torch.full((B, K), -float("inf"), dtype=torch.float32, device=dev)
+    score[:, 0] = 0.0  # the K rows of a prompt start identical: only the first may branch
+    state = [score.view(R), *torch.zeros((2, R), dtype=torch.int32, device=dev), None]  # score, fin, glen, all_done
+    tok_hist = torch.empty((max(new, 1), R), dtype=torch.int64, device=dev)
+    par_hist = torch.empty((max(new, 1), R), dtype=torch.int32, device=dev)
+    steps = 0
+    if new > 0:
+        with eval_stages(stages):
+            caches = [m.new_cache(*st.prompts.shape) for m in stages]
+            x = st.prompts
+            for s, m in enumerate(stages):
+                x = m.prefill(x, caches[s], lens=st.lens_dev, head_rows=K if s == P - 1 else 1)
+            forks = [m.beam_cache(caches[s], K, new) for s, m in enumerate(stages)]
+
+            def sample(logits, t):
+                tok, par, *state[:] = beam_step(logits, sp.vocab, K, *state[:3], sp.eos, sp.pad, tok_hist[t],
+                                                par_hist[t])
+                return tok, par
+
+            def advance(tp, t):
+                x, par = tp
+                for m, fork in zip(stages, forks):
+                    fork.reparent(par)
+                    x = m.decode_step_forked(x, fork)
+                return x
+            steps = decode_loop(x, new, check, sample, advance, lambda: bool(state[3].item()))
+    score, _, glen, _ = state
+    beam_backtrack(st.out, st.lens0, tok_hist, par_hist, glen, steps, K, sp.pad)
+    # the final ranking, once per call: score / length ** length_penalty in fp64, the lowest beam first on ties
+    rank = score.double() / glen.clamp(min=1).double().pow(float(length_penalty))
+    order = torch.sort(rank.view(B, K), dim=1, descending=True, stable=True).indices
+    rows = (torch.arange(B, device=dev)[:, None] * K + order).reshape(R)
+    return st.out[rows], (st.lens0 + glen)[rows], st.lens0, steps, score[rows]
+
+
 def _generate_lookup(engine, st: TokenState, sp: Sampling, new: int, every: int, K: int, ngram: int):
     """The driver of ``lookup`` = K > 0 (one rank): the prefill and the first token as always, then verify steps of
     K + 1 positions per row; every ``every`` steps the host reads one flag (are all rows done or full?)."""
@@ -334,7 +422,8 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
              seed: Optional[int] = None, sample0: int = 0, top_p: float = 1.0, prompt_lens=None,
              eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
              graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False,
-             prefill_chunk: int = 0, num_samples: int = 1):
+             prefill_chunk: int = 0, num_samples: int = 1, num_beams: int = 1, length_penalty: float = 0.0,
+             return_beams: bool = False):
     """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
     ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
     samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
@@ -353,7 +442,11 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     (parallel/session.py) that lives for this call; 0 runs the lines it always ran. ``num_samples`` = n in 2..64 (one
     rank, not with ``graph``, ``lookup`` or ``prefill_chunk``): n continuations of every prompt from one prefill and
     one copy of the prompt's keys; the result has B n rows, row b n + j sibling j of prompt b, and is that of the call
-    on ``prompts.repeat_interleave(n, 0)`` bit for bit (module docstring); 1 runs the lines it always ran."""
+    on ``prompts.repeat_interleave(n, 0)`` bit for bit (module docstring); 1 runs the lines it always ran.
+    ``num_beams`` = K in 2..8 (one rank, greedy arguments only, not with ``num_samples``, ``graph``, ``lookup`` or
+    ``prefill_chunk``): beam search (module docstring). The result is each prompt's best hypothesis under
+    ``score / length ** length_penalty``; ``return_beams``: all [B K, ...] rows, best first per prompt, and their
+    scores fp32 [B K] appended to the result; 1 runs the lines it always ran."""
     from ..models.gpt2 import dropout_seed
 
     new = int(max_new_tokens)
@@ -368,6 +461,8 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     if return_stats and graph:
         raise ValueError("generate: return_stats is not available with graph=True")
     _check_samples(engine, num_samples, graph, lookup, prefill_chunk)
+    _check_beams(engine, cfg, prompts.shape[0], num_beams, temperature, top_k, top_p, num_samples,
+                 graph, lookup, prefill_chunk)
     if graph:
         check_graph(engine, cfg)
     sp = Sampling(cfg.vocab_size, temperature, top_k, top_p, dropout_seed(0 if seed is None else seed), sample0,
@@ -376,6 +471,15 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     # the step kernel (sample + bookkeeping in one launch) serves these arguments; without them the host stores a column
     stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0
     state = partial(TokenState, prompts, lens_host, prompts.shape[1] + new, sp.pad, engine.device)
+    if num_beams > 1:
+        K = num_beams
+        *res, scores = _generate_beam(engine, state(repeat=K), sp, new, check, K, float(length_penalty))
+        if not return_beams:  # the best hypothesis of every prompt
+            res[:3] = [t[::K].contiguous() for t in res[:3]]
+        res = result(*res[:3], return_lengths, return_stats, *res[3:])
+        if return_beams:
+            res = (res if isinstance(res, tuple) else (res,)) + (scores,)
+        return res
     if prefill_chunk > 0:
         res = _generate_chunked(engine, prompts, lens_host, new, sp, check, prefill_chunk)
     elif new == 0:  # nothing to draw in any other mode: the prompts come back, cleaned where the mode steps
