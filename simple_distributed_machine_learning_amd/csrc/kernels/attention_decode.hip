@@ -159,6 +159,10 @@ void attention_decode_bf16(const AttnDecodeArgs& a, hipStream_t stream) {
     return;
   }
   hipLaunchKernelGGL(attn_decode_chunk_kernel<false>, dim3(a.max_chunks, a.H, a.B), dim3(64), 0, stream, a);
+  attention_decode_combine(a, stream);
+}
+
+void attention_decode_combine(const AttnDecodeArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(a.H, a.B), dim3(64), 0, stream, a);
 }
 

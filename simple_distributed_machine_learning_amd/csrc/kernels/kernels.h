@@ -519,6 +519,28 @@ struct AttnDecodeArgs {
 };
 int attention_decode_chunks(int n_keys);
 void attention_decode_bf16(const AttnDecodeArgs& a, hipStream_t stream);
+// The second launch of the two-launch form alone: the slots of every (b, h) in chunk order to out (reads lens, ws_ml,
+// ws_o, B, H, Smax, max_chunks of `a`). attention_decode_fp8.hip's chunks write attn_chunk.h's slots and call this.
+void attention_decode_combine(const AttnDecodeArgs& a, hipStream_t stream);
+// ---- fp8 KV cache (kv_fp8.h, kv_quantize.hip, attention_decode_fp8.hip; ops/decode.py kv_quantize is the format) ----
+// A cache row (sample, key, head) is 64 OCP e4m3 bytes and one int8 exponent e: value = e4m3(byte) * 2^e, e the
+// smallest integer with amax * 2^-e <= 448, clamped to [-120, 120], 0 for an all-zero row. k8 / v8 [B][Smax][H][64]
+// uint8 and ke / ve [B][H][Smax] int8, all contiguous.
+// kv_quantize_rows: the k and v of positions 0..S-1 of qkv [B][S] rows (row stride ldq, sample stride sqb, elements)
+// to the cache, one launch. attention_decode_fp8: attention_decode_bf16's semantics on that cache, two launches; the
+// new token's k, v are quantised from qkv, written to row lens[b] (bytes and exponent) and scored as dequantised.
+struct KvFp8Args {
+  const void* qkv = nullptr;
+  void *k8 = nullptr, *v8 = nullptr, *out = nullptr;
+  signed char *ke = nullptr, *ve = nullptr;
+  const int* lens = nullptr;
+  float *ws_ml = nullptr, *ws_o = nullptr;
+  int B = 0, H = 0, S = 0, Smax = 0, max_chunks = 0;
+  long ldq = 0, sqb = 0;
+  float scale = 1.f;
+};
+void kv_quantize_rows_fp8(const KvFp8Args& a, hipStream_t stream);
+void attention_decode_fp8(const KvFp8Args& a, hipStream_t stream);
 // T = 1 .. kAttnAppendMaxT new tokens per sample against the cache (attention_append.hip). qkv [B][T] rows of ldq
 // elements, nq [B] int32 on the device: live queries per sample. Query t is live iff t < nq[b] and lens[b] + t <
 // n_keys (the host's bound, 1 <= n_keys <= Smax; max_chunks = attention_decode_chunks(n_keys)). A live query writes

@@ -2161,6 +2161,78 @@ torch::Tensor attention_decode(torch::Tensor qkv, torch::Tensor k_cache, torch::
   return out;
 }
 
+// an fp8 cache (kernels.h KvFp8Args): k8 / v8 [B, Smax, H, 64] uint8 and ke / ve [B, H, Smax] int8, contiguous, on
+// `like`'s device; fills the args' pointers and B, H, Smax
+static void check_kv_fp8(const char* who, const torch::Tensor& k8, const torch::Tensor& ke, const torch::Tensor& v8,
+                         const torch::Tensor& ve, const torch::Tensor& like, sdml::KvFp8Args& a) {
+  for (const torch::Tensor* t : {&k8, &v8})
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device() && t->scalar_type() == torch::kUInt8 && t->dim() == 4 &&
+                    t->is_contiguous() && aligned16(*t),
+                who, ": k8 / v8 must be contiguous uint8 [B, Smax, H, 64] tensors on qkv's device, got ",
+                t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(k8.size(3) == 64, who, ": head width 64, got ", k8.size(3));
+  TORCH_CHECK(k8.sizes() == v8.sizes(), who, ": k8 ", k8.sizes(), " and v8 ", v8.sizes(), " differ");
+  const int64_t B = k8.size(0), Smax = k8.size(1), H = k8.size(2);
+  for (const torch::Tensor* t : {&ke, &ve})
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device() && t->scalar_type() == torch::kInt8 && t->dim() == 3 &&
+                    t->is_contiguous() && t->size(0) == B && t->size(1) == H && t->size(2) == Smax,
+                who, ": ke / ve must be contiguous int8 [B, H, Smax] = [", B, ", ", H, ", ", Smax,
+                "] tensors on qkv's device, got ", t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(B >= 1 && 2 * B <= 65535 && H >= 1 && H <= 65535 && Smax >= 1 && Smax < (1 << 30), who,
+              ": batch / heads out of the grid's range");
+  a.k8 = k8.data_ptr(), a.v8 = v8.data_ptr();
+  a.ke = ke.data_ptr<int8_t>(), a.ve = ve.data_ptr<int8_t>();
+  a.B = (int)B, a.H = (int)H, a.Smax = (int)Smax;
+}
+
+// qkv [B, S', 3C] bf16 (a layer's fused projection of the prompt): quantises the k and v of positions 0..S-1 into the
+// fp8 cache, rows 0..S-1, in one launch (kv_quantize.hip)
+void kv_quantize_rows(torch::Tensor qkv, torch::Tensor k8, torch::Tensor ke, torch::Tensor v8, torch::Tensor ve,
+                      int64_t S) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 3 && qkv.stride(2) == 1,
+              "kv_quantize_rows: qkv must be a [B, S, 3C] bf16 device tensor with unit column stride");
+  sdml::KvFp8Args a;
+  check_kv_fp8("kv_quantize_rows", k8, ke, v8, ve, qkv, a);
+  TORCH_CHECK(qkv.size(0) == a.B && qkv.size(2) == 3 * 64 * (int64_t)a.H, "kv_quantize_rows: qkv ", qkv.sizes(),
+              " does not match a ", k8.sizes(), " cache");
+  TORCH_CHECK(S >= 0 && S <= qkv.size(1) && S <= a.Smax, "kv_quantize_rows: S = ", S, " positions, but qkv has ",
+              qkv.size(1), " and the cache ", a.Smax, " rows");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && qkv.stride(0) >= 0 && qkv.stride(1) >= 0 &&
+                  aligned16(qkv),
+              "kv_quantize_rows: 16-byte aligned rows required");
+  a.qkv = qkv.data_ptr();
+  a.S = (int)S, a.sqb = qkv.stride(0), a.ldq = qkv.stride(1);
+  sdml::kv_quantize_rows_fp8(a, cur_stream());
+}
+
+// attention_decode on an fp8 cache (attention_decode_fp8.hip): qkv [B, 3C] bf16, lens int32 [B], n_keys the host's
+// bound lens[b] + 1 <= n_keys <= Smax. Quantises the new k, v into cache row lens[b]; returns [B, C] bf16.
+torch::Tensor attention_decode_fp8(torch::Tensor qkv, torch::Tensor k8, torch::Tensor ke, torch::Tensor v8,
+                                   torch::Tensor ve, torch::Tensor lens, double scale, int64_t n_keys) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1,
+              "attention_decode_fp8: qkv must be a [B, 3C] bf16 device tensor with unit column stride");
+  sdml::KvFp8Args a;
+  check_kv_fp8("attention_decode_fp8", k8, ke, v8, ve, qkv, a);
+  const int64_t B = a.B, H = a.H, C = H * 64;
+  TORCH_CHECK(qkv.size(0) == B && qkv.size(1) == 3 * C, "attention_decode_fp8: qkv ", qkv.sizes(),
+              " does not match a ", k8.sizes(), " cache");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && qkv.stride(0) >= 0 && aligned16(qkv),
+              "attention_decode_fp8: 16-byte aligned rows required");
+  a.lens = device_i32("attention_decode_fp8", "lens", "B", lens, B, qkv);
+  TORCH_CHECK(n_keys >= 1 && n_keys <= a.Smax, "attention_decode_fp8: the cache is full: ", n_keys,
+              " keys with the new one, ", a.Smax, " rows (lens[b] + 1 <= n_keys <= Smax)");
+  a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
+  auto out = torch::empty({B, C}, qkv.options());
+  auto ws = torch::empty({B * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
+  a.qkv = qkv.data_ptr(), a.out = out.data_ptr();
+  a.ws_o = ws.data_ptr<float>();
+  a.ws_ml = a.ws_o + B * H * a.max_chunks * 64;
+  a.ldq = qkv.stride(0);
+  a.scale = (float)scale;
+  sdml::attention_decode_fp8(a, cur_stream());
+  return out;
+}
+
 // qkv [B, T, 3C] (T = 1..8 new tokens per sample), the caches as attention_decode takes them, lens / nq int32 [B] on
 // the device: keys already cached and live queries per sample. Query t is live iff t < nq[b] and lens[b] + t <
 // n_keys. Writes the live queries' k, v at cache rows lens[b] + t; returns [B, T, C], zeros for dead queries.
@@ -2599,6 +2671,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one new token per sample against a KV cache (bf16, d=64): writes k, v at row lens[b], returns [B, C]",
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("n_keys"),
         py::arg("tickets") = py::none());
+  m.def("attention_decode_fp8", &attention_decode_fp8,
+        "attention_decode on an fp8 KV cache (e4m3 bytes [B, Smax, H, 64] + int8 row exponents [B, H, Smax]): "
+        "quantises and writes k, v at row lens[b], returns [B, C]",
+        py::arg("qkv"), py::arg("k8"), py::arg("ke"), py::arg("v8"), py::arg("ve"), py::arg("lens"), py::arg("scale"),
+        py::arg("n_keys"));
+  m.def("kv_quantize_rows", &kv_quantize_rows,
+        "the k and v of positions 0..S-1 of qkv [B, S', 3C] bf16 into an fp8 KV cache, one launch",
+        py::arg("qkv"), py::arg("k8"), py::arg("ke"), py::arg("v8"), py::arg("ve"), py::arg("S"));
   m.def("attention_append", &attention_append,
         "T = 1..8 new tokens per sample against a KV cache (bf16, d=64): writes the live queries' k, v at rows "
         "lens[b] + t, returns [B, T, C] with attention_decode's bits per query",

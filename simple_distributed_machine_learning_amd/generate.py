@@ -17,7 +17,8 @@ drafted from the row's own history, matched on its last N tokens; the same token
 then counts verify steps. ``--num_samples N`` prints N continuations of every prompt, the N lines of the first prompt
 first (one rank; the prompt is prefilled and its keys are stored once). ``--metrics`` gets one ``generate`` event: the
 tokens really generated over all rows, seconds, tokens/s, graph, lookup, lookup_ngram, steps, tokens per step and
-num_samples.
+num_samples. ``--kv_dtype fp8`` keeps the KV cache as e4m3 bytes with one exponent per row (half the bytes a decode
+step streams; the plain loop and ``--graph`` only); the event carries ``kv_dtype``.
 """
 from __future__ import annotations
 
@@ -95,6 +96,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --num_beams: rank a prompt's hypotheses by score / length ** this (0: the raw score)")
     s.add_argument("--return_beams", action="store_true",
                    help="with --num_beams: print all K hypotheses of every prompt, best first")
+    s.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"],
+                   help="the KV cache's storage: fp8 is e4m3 bytes with one int8 exponent per row, 66 bytes for 128 "
+                        "(not with --lookup, --num_samples, --num_beams or --prefill_chunk)")
     return p
 
 
@@ -169,7 +173,7 @@ def run(args) -> dict:
                        return_lengths=True, graph=args.graph, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
                        return_stats=not args.graph, prefill_chunk=args.prefill_chunk, num_samples=args.num_samples,
                        num_beams=args.num_beams, length_penalty=args.length_penalty,
-                       return_beams=args.return_beams and args.num_beams > 1)
+                       return_beams=args.return_beams and args.num_beams > 1, kv_dtype=args.kv_dtype)
         out, lengths = res[0], res[1]
         steps = res[2]["steps"] if len(res) > 2 and isinstance(res[2], dict) else None
         rows = out.cpu().tolist()  # (the read-back ends the timed region)
@@ -191,7 +195,7 @@ def run(args) -> dict:
                     tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k,
                     top_p=args.top_p, graph=bool(args.graph), lookup=args.lookup, lookup_ngram=args.lookup_ngram,
                     steps=steps, tokens_per_step=None if not steps else n_new / steps,
-                    num_samples=args.num_samples, num_beams=args.num_beams)
+                    num_samples=args.num_samples, num_beams=args.num_beams, kv_dtype=args.kv_dtype)
     return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
 
 

@@ -29,9 +29,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .base import ModelSpec, PipelineStage
-from ..ops.decode import (ATTENTION_APPEND_MAX_T, ATTENTION_FORK_MAX_N, BEAM_MAX_K, LINEAR_DECODE_MAX_M,
-                          attention_append, attention_decode, attention_extend, attention_fork, beam_gather_kv,
-                          embedding_at, linear_decode)
+from ..ops.decode import (ATTENTION_APPEND_MAX_T, ATTENTION_FORK_MAX_N, BEAM_MAX_K, KV_DTYPES, LINEAR_DECODE_MAX_M,
+                          attention_append, attention_decode, attention_decode_fp8, attention_extend, attention_fork,
+                          beam_gather_kv, embedding_at, kv_quantize_rows, linear_decode)
 from ..ops.linear import Linear, _w_padded, linear, lm_head, mlp_gelu
 from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
                              dropout_threshold)
@@ -270,11 +270,15 @@ class GPT2Stage(PipelineStage):
         return lm_head(y, self.lm_head.weight) if last else x
 
     # ---- generation: KV cache, prefill, one decode step (ops/decode.py; parallel/generate.py drives them) ----------
-    def new_cache(self, B: int, Smax: int, fused: bool = False) -> "KVCache":
+    def new_cache(self, B: int, Smax: int, fused: bool = False, kv_dtype: str = "bf16") -> "KVCache":
         """An empty cache for B samples and up to Smax positions: K and V [B, Smax, H, D] per local layer, one
         device-side length. ``fused``: also the arrival counters of ``decode_step(fused=True)``, one zeroed int32
         buffer with a slice of its own per call site (four projections and the attention of every local layer; the
-        lm_head is not split over K and needs none)."""
+        lm_head is not split over K and needs none). ``kv_dtype`` "fp8": K and V are e4m3 bytes, uint8
+        [B, Smax, H, D], with one int8 exponent per row in ``ke`` / ``ve`` [B, H, Smax] (ops/decode.py kv_quantize):
+        66 bytes per row where the parameters' dtype takes 2 D. ``prefill`` and ``decode_step`` serve such a cache."""
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"new_cache: kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
         if Smax > self.cfg.block_size:
             raise ValueError(f"a cache of {Smax} positions exceeds block_size={self.cfg.block_size}")
         if getattr(self, "tp", None) is not None:
@@ -286,8 +290,31 @@ class GPT2Stage(PipelineStage):
         tickets = None
         if fused:
             tickets = torch.zeros(n * sum(self._ticket_sizes(B)), dtype=torch.int32, device=p.device)
-        return KVCache([mk() for _ in range(n)], [mk() for _ in range(n)],
-                       torch.zeros(B, dtype=torch.int32, device=p.device), 0, Smax, tickets)
+        lens = torch.zeros(B, dtype=torch.int32, device=p.device)
+        if kv_dtype == "fp8":
+            mk8 = lambda: torch.empty((B, Smax, H, D), dtype=torch.uint8, device=p.device)  # noqa: E731
+            mke = lambda: torch.empty((B, H, Smax), dtype=torch.int8, device=p.device)  # noqa: E731
+            return KVCache([mk8() for _ in range(n)], [mk8() for _ in range(n)], lens, 0, Smax, tickets, "fp8",
+                           [mke() for _ in range(n)], [mke() for _ in range(n)])
+        return KVCache([mk() for _ in range(n)], [mk() for _ in range(n)], lens, 0, Smax, tickets)
+
+    @staticmethod
+    def _bf16_cache_only(who: str, cache: "KVCache"):
+        if cache.kv_dtype != "bf16":
+            raise ValueError(f"{who}: a kv_dtype={cache.kv_dtype!r} cache is served by prefill and decode_step only")
+
+    @staticmethod
+    def _decode_attention(cache: "KVCache", H: int, n_keys: int, tickets=None):
+        """decode_step's attention call on block i's fused projection, by the cache's kv_dtype."""
+        if cache.kv_dtype == "fp8":
+            if tickets is not None and any(t["attn"] is not None for t in tickets):
+                raise ValueError("decode_step: the attention over an fp8 cache has no one-launch (tickets) form")
+            return lambda i, qkv: attention_decode_fp8(qkv, cache.k[i], cache.ke[i], cache.v[i], cache.ve[i],
+                                                       cache.lens, H, n_keys)
+        if tickets is None:
+            return lambda i, qkv: attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, n_keys)
+        return lambda i, qkv: attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, n_keys,
+                                               tickets=tickets[i]["attn"])
 
     def _ticket_sizes(self, B: int):
         """Counters per call site of one layer (DECODE_SITES order): a projection has one per 16 output columns, the
@@ -391,8 +418,11 @@ class GPT2Stage(PipelineStage):
 
         def attn(i, blk, y):
             qkv = blk.attn.c_attn(y)
-            cache.k[i][:, :S].copy_(qkv[..., C:2 * C].view(B, S, H, C // H))
-            cache.v[i][:, :S].copy_(qkv[..., 2 * C:].view(B, S, H, C // H))
+            if cache.kv_dtype == "fp8":  # (the flash kernel below still reads the prompt's unquantised k and v)
+                kv_quantize_rows(qkv, cache.k[i], cache.ke[i], cache.v[i], cache.ve[i], S)
+            else:
+                cache.k[i][:, :S].copy_(qkv[..., C:2 * C].view(B, S, H, C // H))
+                cache.v[i][:, :S].copy_(qkv[..., 2 * C:].view(B, S, H, C // H))
             return blk.attn.c_proj(causal_attention(qkv, H))
 
         x, y = self._layers(x, attn, lambda i, blk, y: blk.mlp(y))
@@ -424,6 +454,7 @@ class GPT2Stage(PipelineStage):
         min(n + T, smax). Returns [B, T, C], or on the last stage the logits [B, ld] of each sample's last live
         position (row nq[b] - 1, gathered on the device before the lm_head); the row of a sample with nq[b] == 0
         holds unspecified values."""
+        self._bf16_cache_only("extend", cache)
         if x.dim() < 2 or x.shape[1] < 1:
             raise ValueError(f"extend: x must be [B, T(, C)] with T >= 1, got {tuple(x.shape)}")
         B, T = x.shape[0], x.shape[1]
@@ -472,8 +503,7 @@ class GPT2Stage(PipelineStage):
         if self.stage_id == 0:
             x = embedding_at(x, cache.lens, self.wte.weight, self.wpe.weight)
         H = self.cfg.n_head
-        x, y = self._layers(x, *self._decode_lines(
-            lambda i, qkv: attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, cache.n + 1)))
+        x, y = self._layers(x, *self._decode_lines(self._decode_attention(cache, H, cache.n + 1)))
         cache.lens.add_(1)
         cache.n += 1
         return self._head_logits(self._normed(x, y)) if self.is_last else x
@@ -483,6 +513,7 @@ class GPT2Stage(PipelineStage):
         prefix (its ``lens`` are the prompt lengths; it is only read from here on), and every row b n + j, sibling j
         of prompt b, gets ``nmax`` suffix positions of its own per local layer. ``cache.n + nmax`` may not exceed
         block_size. ``suffix`` = (ks, vs): the caller's storage for the suffixes (``beam_cache``), not new tensors."""
+        self._bf16_cache_only("fork_cache", cache)
         if isinstance(n_samples, bool) or not isinstance(n_samples, int) or not 1 <= n_samples <= ATTENTION_FORK_MAX_N:
             raise ValueError(f"fork_cache: n_samples must be an integer in 1..{ATTENTION_FORK_MAX_N}, got {n_samples!r}")
         if cache.n < 1:
@@ -502,6 +533,7 @@ class GPT2Stage(PipelineStage):
         ``ks`` / ``vs`` are views into the current half, and ``reparent(par)`` copies row (b, par[r])'s positions in
         use into row r of the other half in one launch (ops/decode.py beam_gather_kv) and makes that half current.
         ``decode_step_forked`` takes the result as it takes a forked cache."""
+        self._bf16_cache_only("beam_cache", cache)
         if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= BEAM_MAX_K:
             raise ValueError(f"beam_cache: K must be an integer in 2..{BEAM_MAX_K}, got {K!r}")
         p = next(self.parameters())
@@ -546,6 +578,7 @@ class GPT2Stage(PipelineStage):
         stages of one rank must share one ``cache.lens`` tensor. ``cache.n`` becomes the host's bound min(n + T,
         smax). On ROCm bf16 B * T <= 64 is required (``linear_decode``'s rows): more rows would take another GEMM
         with other bits, and are refused."""
+        self._bf16_cache_only("decode_block", cache)
         if x.dim() < 2 or not 1 <= x.shape[1] <= ATTENTION_APPEND_MAX_T:
             raise ValueError(f"decode_block: x must be [B, T(, C)] with T in 1..{ATTENTION_APPEND_MAX_T}, got "
                              f"{tuple(x.shape)}")
@@ -584,9 +617,7 @@ class GPT2Stage(PipelineStage):
             x = embedding_at(x, cache.lens, self.wte.weight, self.wpe.weight)
         H = self.cfg.n_head
         tk = [{s: (v if s in sites else None) for s, v in d.items()} for d in views]
-        x, y = self._layers(x, *self._decode_lines(
-            lambda i, qkv: attention_decode(qkv, cache.k[i], cache.v[i], cache.lens, H, cache.smax,
-                                            tickets=tk[i]["attn"]), tk))
+        x, y = self._layers(x, *self._decode_lines(self._decode_attention(cache, H, cache.smax, tk), tk))
         cache.lens.add_(1)
         cache.n += 1
         return self._head_logits(self._normed(x, y)) if self.is_last else x
@@ -603,13 +634,17 @@ class KVCache:
     """A stage's generation state: per local layer K and V [B, Smax, H, D]; ``lens`` int32 [B] on the device (keys
     cached per sample, what the kernels read); ``n`` the host's bound on them (the count itself after an equal-length
     prefill, the longest row's after a ragged one; all samples advance together), so the bounds are checked without
-    reading the device."""
+    reading the device. ``kv_dtype`` "fp8": ``k`` / ``v`` hold e4m3 bytes (uint8) and ``ke`` / ``ve`` the rows' int8
+    exponents [B, H, Smax] per local layer (ops/decode.py kv_quantize)."""
     k: list
     v: list
     lens: torch.Tensor
     n: int
     smax: int
     tickets: Optional[torch.Tensor] = None  # new_cache(fused=True): the arrival counters of decode_step(fused=True)
+    kv_dtype: str = "bf16"
+    ke: Optional[list] = None
+    ve: Optional[list] = None
 
 
 @dataclass

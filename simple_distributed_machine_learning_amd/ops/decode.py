@@ -1,5 +1,6 @@
 """Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, attention_append.hip,
-attention_extend.hip, attention_fork.hip, linear_decode.hip, sample.hip, lookup.hip, beam.hip) and their torch twins.
+attention_extend.hip, attention_fork.hip, attention_decode_fp8.hip, kv_quantize.hip, linear_decode.hip, sample.hip,
+lookup.hip, beam.hip) and their torch twins.
 
 Dispatch: ROCm bf16 tensors (head width 64 for the attention) run the hand-written kernels, and a shape the kernels do
 not take is an error there, never a library call. CPU tensors, fp32 and other head widths run the twins below, which
@@ -88,6 +89,9 @@ def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int, tick
     rows concerned are not written and their counters are left non-zero, so zero the tensor before using it again
     (``decode_step`` passes Smax and zeroes its buffer every step). The torch twin ignores it."""
     Smax = k_cache.shape[1]
+    if k_cache.dtype == torch.uint8:
+        raise ValueError("attention_decode: an fp8 cache goes through attention_decode_fp8, which has no one-launch "
+                         "(tickets) form")
     if not 1 <= n_keys <= Smax:
         raise ValueError(f"attention_decode: {n_keys} keys with the new one, but the cache has {Smax} rows")
     D = k_cache.shape[-1]
@@ -96,6 +100,106 @@ def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int, tick
             return kernels().attention_decode(qkv, k_cache, v_cache, lens, 1.0 / math.sqrt(D), int(n_keys), tickets)
         return kernels().attention_decode(qkv, k_cache, v_cache, lens, 1.0 / math.sqrt(D), int(n_keys))
     return attention_decode_ref(qkv, k_cache, v_cache, lens, n_head, n_keys)
+
+
+# ---- fp8 KV cache (csrc/kernels/kv_fp8.h, kv_quantize.hip, attention_decode_fp8.hip; docs/NUMERICS.md) ---------------
+KV_DTYPES = ("bf16", "fp8")
+KV_EXP_MIN, KV_EXP_MAX = -120, 120  # kv_fp8.h kExpMin, kExpMax
+
+
+def _pow2(e):
+    """2^e as fp32 for an integer tensor e in [-126, 127], from the exponent field: exact on every device."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def kv_quantize(x):
+    """The fp8 KV-cache format, which the kernels reproduce bit for bit. x [..., D]: rows of D channels. Returns
+    (bytes uint8 [..., D], exps int8 [...]): a row is OCP e4m3 bytes and one exponent e, value = e4m3(byte) * 2^e.
+    e is the smallest integer with amax * 2^-e <= 448 (amax = f 2^x, f in [1, 2): x - 8 if f <= 1.75, else x - 7),
+    clamped to [-120, 120], and 0 for an all-zero row: the scaled row peaks in (224, 448], e4m3's top binade, and never
+    overflows. x * 2^-e is exact, so the e4m3 round-to-nearest-even is the only rounding."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    f, ex = torch.frexp(amax)  # amax = f 2^ex with f in [0.5, 1)
+    e = ex - 1 - torch.where(f <= 0.875, 8, 7)
+    e = torch.where(amax == 0, torch.zeros_like(e), e.clamp(KV_EXP_MIN, KV_EXP_MAX))
+    q = (xf * _pow2(-e)[..., None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    return q, e.to(torch.int8)
+
+
+def kv_dequantize(q, e):
+    """fp32 [..., D] = e4m3(q) * 2^e for bytes uint8 [..., D] and exponents int8 [...]: exact."""
+    return q.view(torch.float8_e4m3fn).float() * _pow2(e)[..., None]
+
+
+def _check_kv_fp8(who: str, qkv, k8, ke, v8, ve):
+    B, Smax, H = k8.shape[:3] if k8.dim() == 4 else (0, 0, 0)
+    if k8.dim() != 4 or k8.shape != v8.shape or ke.shape != (B, H, Smax) or ve.shape != ke.shape or \
+            k8.dtype != torch.uint8 or v8.dtype != torch.uint8 or ke.dtype != torch.int8 or ve.dtype != torch.int8:
+        raise ValueError(f"{who}: an fp8 cache is k8 / v8 uint8 [B, Smax, H, D] with ke / ve int8 [B, H, Smax], got "
+                         f"{k8.dtype} {tuple(k8.shape)}, {ke.dtype} {tuple(ke.shape)}, {v8.dtype} {tuple(v8.shape)}, "
+                         f"{ve.dtype} {tuple(ve.shape)}")
+    if qkv.shape[0] != B or qkv.shape[-1] != 3 * H * k8.shape[3]:
+        raise ValueError(f"{who}: qkv {tuple(qkv.shape)} does not match a {tuple(k8.shape)} cache")
+
+
+def kv_quantize_rows_ref(qkv, k8, ke, v8, ve, S: int):
+    """The twin: ``kv_quantize`` of the k and v of positions 0..S-1 of qkv [B, S', 3C] into cache rows 0..S-1."""
+    B, _, H, D = k8.shape
+    C = H * D
+    for o, (q8, ex) in enumerate(((k8, ke), (v8, ve)), 1):
+        q, e = kv_quantize(qkv[:, :S, o * C:(o + 1) * C].reshape(B, S, H, D))
+        q8[:, :S] = q
+        ex[:, :, :S] = e.transpose(1, 2)
+
+
+def kv_quantize_rows(qkv, k8, ke, v8, ve, S: int):
+    """Prefill's write of an fp8 cache: the k and v of positions 0..S-1 of a layer's fused projection qkv [B, S', 3C]
+    become the bytes k8 / v8 [B, Smax, H, D] uint8 and exponents ke / ve [B, H, Smax] int8 of rows 0..S-1
+    (``kv_quantize`` is the format). ROCm bf16 with D = 64: kv_quantize.hip, one launch for both operands."""
+    _check_kv_fp8("kv_quantize_rows", qkv, k8, ke, v8, ve)
+    if qkv.dim() != 3 or not 0 <= S <= min(qkv.shape[1], k8.shape[1]):
+        raise ValueError(f"kv_quantize_rows: S = {S} positions of qkv {tuple(qkv.shape)} into a cache of "
+                         f"{k8.shape[1]} rows")
+    if _hip_bf16(qkv) and k8.is_cuda and k8.shape[-1] == 64:
+        return kernels().kv_quantize_rows(qkv, k8, ke, v8, ve, int(S))
+    return kv_quantize_rows_ref(qkv, k8, ke, v8, ve, int(S))
+
+
+def attention_decode_fp8_ref(qkv, k8, ke, v8, ve, lens, n_head: int, n_keys: int):
+    """The twin: quantise the new k, v (``kv_quantize``) and write bytes and exponents at cache row lens[b]; then
+    ``attention_decode_ref``'s lines on the dequantised cache, the new row included as dequantised. Rows at or past
+    lens[b] other than the new one are selected away there (they may hold NaN bytes)."""
+    B, C3 = qkv.shape
+    C = C3 // 3
+    D = C // n_head
+    idx = lens.to(torch.int64)
+    rows = torch.arange(B, device=qkv.device)
+    new = [qkv[:, :C].float()]
+    for o, (q8, ex) in enumerate(((k8, ke), (v8, ve)), 1):
+        q, e = kv_quantize(qkv[:, o * C:(o + 1) * C].view(B, n_head, D))
+        q8[rows, idx] = q
+        ex[rows, :, idx] = e
+        new.append(kv_dequantize(q, e).reshape(B, C))
+    kd = kv_dequantize(k8[:, :n_keys], ke[:, :, :n_keys].transpose(1, 2))
+    vd = kv_dequantize(v8[:, :n_keys], ve[:, :, :n_keys].transpose(1, 2))
+    return attention_decode_ref(torch.cat(new, 1), kd, vd, lens, n_head, n_keys).to(qkv.dtype)
+
+
+def attention_decode_fp8(qkv, k8, ke, v8, ve, lens, n_head: int, n_keys: int):
+    """``attention_decode`` on an fp8 KV cache: k8 / v8 [B, Smax, H, D] uint8 with ke / ve [B, H, Smax] int8
+    (``kv_quantize`` is the format; all four contiguous). The new token's k and v are quantised, written to cache row
+    lens[b], bytes and exponent, and scored as the dequantised row, so the result is the attention over the cache as
+    later steps read it. Returns [B, C]; ``lens`` is not changed; ``n_keys`` as ``attention_decode`` takes it. ROCm
+    bf16 with D = 64: attention_decode_fp8.hip and attention_decode.hip's combine, two launches (there is no
+    one-launch form: ``attention_decode(..., tickets=)`` refuses an fp8 cache)."""
+    _check_kv_fp8("attention_decode_fp8", qkv, k8, ke, v8, ve)
+    Smax = k8.shape[1]
+    if not 1 <= n_keys <= Smax:
+        raise ValueError(f"attention_decode_fp8: {n_keys} keys with the new one, but the cache has {Smax} rows")
+    if _hip_bf16(qkv) and k8.is_cuda and k8.shape[-1] == 64:
+        return kernels().attention_decode_fp8(qkv, k8, ke, v8, ve, lens, 1.0 / math.sqrt(64), int(n_keys))
+    return attention_decode_fp8_ref(qkv, k8, ke, v8, ve, lens, n_head, n_keys)
 
 
 def _check_lens_nq(who: str, B: int, lens, nq):

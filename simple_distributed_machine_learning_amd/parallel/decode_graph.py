@@ -17,7 +17,8 @@ tokens and lengths are those of the eager call bit for bit.
 
 A session (the static token / out / done / length buffers, the KV caches with their counters, the graph) stays on the
 engine as ``engine.decode_session``; at most one. The next call with the same key, (B, total width, temperature,
-top_k, top_p, seed, sample0, eos, pad, the parameters' storage addresses), replays it without capturing again; any
+top_k, top_p, seed, sample0, eos, pad, kv_dtype, the parameters' storage addresses),
+replays it without capturing again; any
 other key replaces it. The weights are read in place, so optimizer steps between two calls need no new capture as long
 as the storages stay. ``engine.decode_graph_captures`` counts the captures.
 
@@ -50,12 +51,13 @@ def check_graph(engine, cfg) -> None:
 class DecodeSession:
     """The static state of one captured decode step; see the module docstring."""
 
-    def __init__(self, engine, key, B: int, total: int, _sites=None):
+    def __init__(self, engine, key, B: int, total: int, _sites=None, kv_dtype: str = "bf16"):
         """``_sites`` (tools/bench_generate.py only): the call sites on one launch, None: models/gpt2.py's."""
         dev = engine.device
         self.key, self.B, self.total, self._sites = key, B, total, _sites
         self.stage_ids = sorted(engine.stages)
-        self.caches = {s: engine.stages[s].new_cache(B, total, fused=True) for s in self.stage_ids}
+        self.caches = {s: engine.stages[s].new_cache(B, total, fused=True, kv_dtype=kv_dtype)
+                       for s in self.stage_ids}
         self.tok = torch.zeros(B, dtype=torch.int64, device=dev)  # the token the next replay embeds
         self.out = torch.zeros((B, total), dtype=torch.int64, device=dev)
         self.done = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -104,20 +106,20 @@ def _param_addresses(engine):
 
 
 @torch.no_grad()
-def generate_graphed(engine, prompts, lens_host, new: int, sampling: Sampling, check: int):
+def generate_graphed(engine, prompts, lens_host, new: int, sampling: Sampling, check: int, kv_dtype: str = "bf16"):
     """generate()'s driver for ``graph=True`` on one rank holding every stage; the arguments are already checked.
     Returns (tokens, lengths, prompt lengths, steps)."""
     B, total = prompts.shape[0], prompts.shape[1] + new
     sp = replace(sampling, temperature=float(sampling.temperature), top_k=int(sampling.top_k),
                  top_p=float(sampling.top_p), sample0=int(sampling.sample0))
-    key = (B, total) + astuple(sp)[1:] + (_param_addresses(engine),)
+    key = (B, total) + astuple(sp)[1:] + (kv_dtype, _param_addresses(engine))
     stage_ids = sorted(engine.stages)
     with eval_stages([engine.stages[s] for s in stage_ids]):
         ses = engine.decode_session
         if ses is None or ses.key != key:
             engine.decode_session = None  # (the old session's memory goes before the new one's is taken)
             del ses
-            ses = DecodeSession(engine, key, B, total)
+            ses = DecodeSession(engine, key, B, total, kv_dtype=kv_dtype)
             ses.capture(engine, sp)
             engine.decode_session = ses
         ses.reset()

@@ -63,6 +63,14 @@ cumulative log-probabilities). It is refused with sampling (``temperature > 0``,
 ``num_samples > 1``, ``graph=True``, ``lookup > 0``, ``prefill_chunk > 0`` and pp > 1; on the kernels B K may not
 exceed 64 rows (the decode projections' bound) and the vocabulary 65536.
 
+``kv_dtype="fp8"`` stores every stage's KV cache as e4m3 bytes with one int8 exponent per (sample, key, head) row
+(ops/decode.py ``kv_quantize``: 66 bytes per row for 128): the prefill quantises the prompt's k and v in one launch per
+layer and every decode step runs ``attention_decode_fp8``, which streams half the bytes. The numerics are those of the
+format (docs/NUMERICS.md "fp8 KV cache"), so the tokens may differ from ``"bf16"``'s; a row's tokens still do not
+depend on the batch, and ``graph=True`` replays them bit for bit. It serves the plain loop (any pp, ragged prompts,
+eos, top-k, top-p) and ``graph=True``; it is refused with ``lookup > 0``, ``num_samples > 1``, ``num_beams > 1``,
+``prefill_chunk > 0`` and by ``GenerationSession``. ``"bf16"`` (the default) runs the lines it always ran.
+
 Limitations: tensor parallelism, data parallelism and ``--schedule rotate`` are refused. With pp ranks one rank works
 at a time (a token must leave the last stage before stage 0 can embed it); several sample groups in flight would fill
 the bubble and are not implemented. ``graph=True`` is refused with pp > 1: the step's boundaries cross ranks between
@@ -82,8 +90,9 @@ from typing import Optional
 
 import torch
 
-from ..ops.decode import (ATTENTION_FORK_MAX_N, BEAM_MAX_K, BEAM_MAX_ROWS, BEAM_MAX_VOCAB, LINEAR_DECODE_MAX_M,
-                          LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, beam_backtrack, beam_step, lookup_step)
+from ..ops.decode import (ATTENTION_FORK_MAX_N, BEAM_MAX_K, BEAM_MAX_ROWS, BEAM_MAX_VOCAB, KV_DTYPES,
+                          LINEAR_DECODE_MAX_M, LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, beam_backtrack, beam_step,
+                          lookup_step)
 from .decode_graph import check_graph, generate_graphed
 from .gen_common import Sampling, TokenState, decode_loop, eval_stages, result
 from .session import GenerationSession
@@ -334,7 +343,21 @@ def _generate_lookup(engine, st: TokenState, sp: Sampling, new: int, every: int,
     return st.out, st.lengths(), st.lens0, steps, row_steps
 
 
-def _generate_pipeline(engine, cfg, st: TokenState, sp: Sampling, new: int, check: int):
+def _check_kv_dtype(kv_dtype, lookup: int, num_samples: int, num_beams: int, prefill_chunk: int):
+    """The refusals of ``kv_dtype``."""
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"generate: kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+    if kv_dtype == "bf16":
+        return
+    for on, what in ((lookup > 0, "lookup > 0 (the verify step's attention reads a bf16 cache)"),
+                     (num_samples > 1, "num_samples > 1 (the fork's attention reads bf16 caches)"),
+                     (num_beams > 1, "num_beams > 1 (the beams' caches are bf16 forks)"),
+                     (prefill_chunk > 0, "prefill_chunk > 0 (the session's extend attention reads a bf16 cache)")):
+        if on:
+            raise ValueError(f"generate: kv_dtype={kv_dtype!r} is not supported with {what}")
+
+
+def _generate_pipeline(engine, cfg, st: TokenState, sp: Sampling, new: int, check: int, kv_dtype: str = "bf16"):
     """The plain driver, on every rank of the pipeline (module docstring)."""
     mesh, dev, P = engine.mesh, engine.device, engine.P
     sched = engine.schedule(1, True)
@@ -401,7 +424,7 @@ def _generate_pipeline(engine, cfg, st: TokenState, sp: Sampling, new: int, chec
         return run_stages(tok if me == first else None, t + 1, prefill=False)
 
     with eval_stages([engine.stages[s] for s in mine]):
-        caches = {s: engine.stages[s].new_cache(B, total) for s in mine}
+        caches = {s: engine.stages[s].new_cache(B, total, kv_dtype=kv_dtype) for s in mine}
         # token index S0 + t (ragged: lens[b] + t); only the last stage's rank samples
         sample = st.sampler(sp, caches[P - 1].lens) if me == last else lambda logits, t: None
         logits = run_stages(st.prompts if me == first else None, 0, prefill=True)
@@ -423,7 +446,7 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
              eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
              graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False,
              prefill_chunk: int = 0, num_samples: int = 1, num_beams: int = 1, length_penalty: float = 0.0,
-             return_beams: bool = False):
+             return_beams: bool = False, kv_dtype: str = "bf16"):
     """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
     ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
     samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
@@ -446,7 +469,8 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     ``num_beams`` = K in 2..8 (one rank, greedy arguments only, not with ``num_samples``, ``graph``, ``lookup`` or
     ``prefill_chunk``): beam search (module docstring). The result is each prompt's best hypothesis under
     ``score / length ** length_penalty``; ``return_beams``: all [B K, ...] rows, best first per prompt, and their
-    scores fp32 [B K] appended to the result; 1 runs the lines it always ran."""
+    scores fp32 [B K] appended to the result; 1 runs the lines it always ran. ``kv_dtype`` "fp8": an 8-bit KV cache
+    (module docstring; the plain loop and ``graph=True`` only); "bf16" runs the lines it always ran."""
     from ..models.gpt2 import dropout_seed
 
     new = int(max_new_tokens)
@@ -463,6 +487,7 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     _check_samples(engine, num_samples, graph, lookup, prefill_chunk)
     _check_beams(engine, cfg, prompts.shape[0], num_beams, temperature, top_k, top_p, num_samples,
                  graph, lookup, prefill_chunk)
+    _check_kv_dtype(kv_dtype, lookup, num_samples, num_beams, prefill_chunk)
     if graph:
         check_graph(engine, cfg)
     sp = Sampling(cfg.vocab_size, temperature, top_k, top_p, dropout_seed(0 if seed is None else seed), sample0,
@@ -488,9 +513,9 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     elif num_samples > 1:
         res = _generate_forked(engine, state(stepped=stepped, repeat=num_samples), sp, new, check, num_samples)
     elif graph:
-        res = generate_graphed(engine, prompts, lens_host, new, sp, check)
+        res = generate_graphed(engine, prompts, lens_host, new, sp, check, kv_dtype)
     elif lookup > 0:
         res = _generate_lookup(engine, state(), sp, new, int(stop_check), lookup, lookup_ngram)
     else:
-        res = _generate_pipeline(engine, cfg, state(stepped=stepped), sp, new, check)
+        res = _generate_pipeline(engine, cfg, state(stepped=stepped), sp, new, check, kv_dtype)
     return result(*res[:3], return_lengths, return_stats, *res[3:])

@@ -68,10 +68,13 @@ class GenerationSession:
     """See the module docstring. One rank; the engine's stages all live on it."""
 
     def __init__(self, engine, prompts, max_len: int, prompt_lens=None, pad_token: int = 0,
-                 seed: Optional[int] = None, sample0: int = 0):
+                 seed: Optional[int] = None, sample0: int = 0, kv_dtype: str = "bf16"):
         from ..models.gpt2 import dropout_seed
         from .generate import _check, _check_step
 
+        if kv_dtype != "bf16":
+            raise ValueError(f"GenerationSession: kv_dtype={kv_dtype!r} is not supported (a session appends and "
+                             "extends its caches, which an fp8 cache does not serve yet); use kv_dtype='bf16'")
         mesh = engine.mesh
         if mesh.pp > 1:
             raise ValueError(f"GenerationSession: pp={mesh.pp} is not supported (the caches of a session live on one "

@@ -37,6 +37,13 @@ hand kernels (the LayerNorm kernels are the same in both). The gate: hand >= lib
     flipped (a one-launch site put back on two launches, a two-launch site put on one). The gate: (c) >= (a) in tokens/s in every round at --B 16 --ctx 512. --sweep adds the B x ctx grid.
 --graph --replays N only captures form (c) and replays it N times: the run to put under `rocprofv3 --kernel-trace
 --stats`, where a kernel's calls / (N + 1) are its launches per step (one eager step precedes the capture).
+
+--kv_dtype fp8 measures only the fp8 KV cache and writes --out_fp8kv, bf16 and fp8 alternated over --rounds:
+  * per-kernel windows: attention_decode_fp8 next to attention_decode at B = 64, ctx 512 / 1024 and B = 16, ctx 512
+    (the gate: at B = 64, ctx 1024 the fp8 kernel is not slower in any round), and kv_quantize_rows next to the two
+    strided copies it replaces at B = 16, S = 512;
+  * the decode loop, eager and graph-replayed, at B = 16, ctx 512 and B = 64, ctx 1024;
+  * the drift of the last-position logits after 128 greedy steps, fp8 teacher-forced on bf16's tokens.
 """
 import argparse
 import json
@@ -435,8 +442,178 @@ def main_graph(a):
     return 0 if ok else 1
 
 
+# ---- the fp8 KV cache (--kv_dtype fp8) -------------------------------------------------------------------------------
+def fp8_cache_like(*shape):
+    """Random e4m3 bytes without a NaN code (0x7F / 0xFF) and small exponents, as a filled cache would hold."""
+    q = torch.randint(0, 0x7F, shape, device=DEV, dtype=torch.uint8)
+    return q | (torch.randint(0, 2, shape, device=DEV, dtype=torch.uint8) << 7)
+
+
+def bench_fp8_kernels(rounds, reps, emit):
+    """attention_decode_fp8 next to attention_decode (operands as in bench_kernels; 66 against 128 bytes per row and
+    operand), and kv_quantize_rows next to the two strided copies it replaces in prefill."""
+    K = _native.kernels()
+    H, D = 12, 64
+    ok = True
+    for B, ctx in ((64, 512), (64, 1024), (16, 512)):
+        Smax = ctx + 1
+        copies = max(2, min(reps, LLC_BYTES // (B * Smax * H * D * 2 * 2) + 1))  # the same count for both dtypes
+        kc = torch.randn(copies, B, Smax, H, D, device=DEV, dtype=BF)
+        vc = torch.randn(copies, B, Smax, H, D, device=DEV, dtype=BF)
+        k8, v8 = fp8_cache_like(copies, B, Smax, H, D), fp8_cache_like(copies, B, Smax, H, D)
+        ke = torch.randint(-8, 8, (copies, B, H, Smax), device=DEV, dtype=torch.int8)
+        ve = torch.randint(-8, 8, (copies, B, H, Smax), device=DEV, dtype=torch.int8)
+        qkv = torch.randn(B, 3 * H * D, device=DEV, dtype=BF)
+        lens = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+        fns = {"attention_decode": lambda i: K.attention_decode(qkv, kc[i % copies], vc[i % copies], lens, 0.125, Smax),
+               "attention_decode_fp8": lambda i: K.attention_decode_fp8(qkv, k8[i % copies], ke[i % copies],
+                                                                        v8[i % copies], ve[i % copies], lens, 0.125,
+                                                                        Smax)}
+        for fn in fns.values():
+            window(fn, copies)
+        us = {k: [] for k in fns}
+        for r in range(rounds):
+            for kname, fn in fns.items():  # alternated
+                ms = window(fn, reps)
+                us[kname].append(round(ms * 1e3, 2))
+                nbytes = B * (ctx + 1) * H * 2 * (D * 2 if kname == "attention_decode" else D + 1)
+                emit({"kernel": kname, "B": B, "H": H, "ctx": ctx, "round": r, "us": us[kname][-1],
+                      "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1), "bytes": nbytes, "copies": copies})
+        rec = {"summary": "attention_decode_fp8 vs attention_decode", "B": B, "ctx": ctx,
+               "bf16_us": us["attention_decode"], "fp8_us": us["attention_decode_fp8"]}
+        if (B, ctx) == (64, 1024):
+            gate = all(f <= b for f, b in zip(us["attention_decode_fp8"], us["attention_decode"]))
+            rec["gate_fp8_not_slower_every_round"] = bool(gate)
+            ok = ok and gate
+        emit(rec)
+        del kc, vc, k8, v8, ke, ve
+    B, S = 16, 512
+    C = H * D
+    qkv = torch.randn(B, S, 3 * C, device=DEV, dtype=BF)
+    kc, vc = (torch.empty(B, S, H, D, device=DEV, dtype=BF) for _ in range(2))
+    k8, v8 = (torch.empty(B, S, H, D, device=DEV, dtype=torch.uint8) for _ in range(2))
+    ke, ve = (torch.empty(B, H, S, device=DEV, dtype=torch.int8) for _ in range(2))
+
+    def copies2(i):
+        kc.copy_(qkv[..., C:2 * C].view(B, S, H, D))
+        vc.copy_(qkv[..., 2 * C:].view(B, S, H, D))
+
+    fns = {"two copy_": copies2, "kv_quantize_rows": lambda i: K.kv_quantize_rows(qkv, k8, ke, v8, ve, S)}
+    for fn in fns.values():
+        window(fn, 10)
+    for r in range(rounds):
+        for kname, fn in fns.items():
+            emit({"kernel": kname, "B": B, "S": S, "H": H, "round": r, "us": round(window(fn, reps) * 1e3, 2)})
+    return ok
+
+
+@torch.no_grad()
+def run_kv_loop(engine, B, ctx, steps, kv_dtype, ses=None):
+    """run_loop / run_graph_loop on a cache of the given kv_dtype, from ctx keys of random contents."""
+    stages = [engine.stages[s] for s in range(engine.P)]
+    ctx = min(ctx, stages[0].cfg.block_size - steps)
+    caches = list(ses.caches.values()) if ses is not None else \
+        [st.new_cache(B, ctx + steps, kv_dtype=kv_dtype) for st in stages]
+    for c in caches:
+        for t in c.k + c.v:
+            if kv_dtype == "fp8":
+                t.copy_(fp8_cache_like(*t.shape))
+            else:
+                t.normal_()
+        for t in (c.ke or []) + (c.ve or []):
+            t.zero_()
+    if ses is not None:
+        return run_graph_loop(ses, ctx, steps)
+    for c in caches:
+        c.lens.fill_(ctx)
+        c.n = ctx
+    V = stages[0].cfg.vocab_size
+    tok = torch.randint(0, V, (B,), device=DEV)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        x = tok
+        for st, c in zip(stages, caches):
+            x = st.decode_step(x, c)
+        tok = sample_logits(x, V, 0.0, 0, 0, 0, caches[-1].lens)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+@torch.no_grad()
+def bench_fp8_loop(engine, B, ctx, steps, rounds, emit):
+    ctx = min(ctx, engine.stages[0].cfg.block_size - steps)
+    forms = [(kv, g) for g in (False, True) for kv in ("bf16", "fp8")]
+    ses = {}
+    for kv, g in forms:
+        if g:
+            ses[kv] = DecodeSession(engine, None, B, ctx + steps, kv_dtype=kv)
+            ses[kv].capture(engine, SAMPLING)
+        run_kv_loop(engine, B, ctx, 8, kv, ses.get(kv) if g else None)
+    tps = {f: [] for f in forms}
+    for r in range(rounds):
+        for kv, g in forms:  # alternated
+            s = run_kv_loop(engine, B, ctx, steps, kv, ses[kv] if g else None)
+            tps[(kv, g)].append(round(B * steps / s, 1))
+            emit({"loop": f"{kv} {'graph' if g else 'eager'}", "B": B, "ctx": ctx, "steps": steps, "round": r,
+                  "ms_per_step": round(s / steps * 1e3, 4), "tokens_per_s": tps[(kv, g)][-1]})
+    emit({"summary": "decode loop, kv_dtype", "B": B, "ctx": ctx,
+          **{f"{kv}_{'graph' if g else 'eager'}_tokens_per_s": v for (kv, g), v in tps.items()}})
+    del ses
+    torch.cuda.empty_cache()
+
+
+@torch.no_grad()
+def fp8_drift(engine, B, S0, steps, emit):
+    """Last-position logits of kv_dtype fp8 against bf16 after `steps` greedy steps, the fp8 run teacher-forced on the
+    bf16 run's tokens (seeded weights, one prompt batch): a measured figure, not a bound."""
+    stages = [engine.stages[s] for s in range(engine.P)]
+    V = stages[0].cfg.vocab_size
+    prompts = torch.randint(0, V, (B, S0), device=DEV, generator=torch.Generator(device=DEV).manual_seed(1))
+    logits, toks = {}, []
+    for kv in ("bf16", "fp8"):
+        caches = [st.new_cache(B, S0 + steps, kv_dtype=kv) for st in stages]
+        x = prompts
+        for st, c in zip(stages, caches):
+            x = st.prefill(x, c)
+        for t in range(steps):
+            if kv == "bf16":
+                toks.append(sample_logits(x, V, 0.0, 0, 0, 0, caches[-1].lens))
+            x = toks[t]
+            for st, c in zip(stages, caches):
+                x = st.decode_step(x, c)
+        logits[kv] = x[:, :V].float()
+    d = logits["fp8"] - logits["bf16"]
+    emit({"summary": "fp8 KV drift", "B": B, "prompt": S0, "steps": steps,
+          "max_abs_diff": round(d.abs().max().item(), 4), "rms_diff": round(d.pow(2).mean().sqrt().item(), 5),
+          "logits_rms": round(logits["bf16"].pow(2).mean().sqrt().item(), 4),
+          "argmax_agree": round((logits["fp8"].argmax(-1) == logits["bf16"].argmax(-1)).float().mean().item(), 3)})
+
+
+def main_fp8kv(a):
+    os.makedirs(os.path.dirname(a.out_fp8kv) or ".", exist_ok=True)
+    with open(a.out_fp8kv, "w") as f:
+        def emit(rec):
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+
+        ok = True if a.no_kernels else bench_fp8_kernels(a.rounds, a.reps, emit)
+        mesh = init_mesh(pp=1, schedule_kind="1f1b", rank=0, world_size=1, device=DEV)
+        engine = PipelineEngine(get_model_spec("gpt2", 2), mesh, schedule_kind="1f1b", num_microbatches=1)
+        engine.eval()
+        for B, ctx in ((16, 512), (64, 1024)):
+            bench_fp8_loop(engine, B, ctx, a.steps, a.rounds, emit)
+        fp8_drift(engine, 16, 64, 128, emit)
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: only the fp8 KV cache's windows, loops and drift, written to --out_fp8kv")
+    ap.add_argument("--out_fp8kv", default="profiles/generate_fp8kv.jsonl")
     ap.add_argument("--B", type=int, default=16)
     ap.add_argument("--ctx", type=int, default=512)
     ap.add_argument("--rounds", type=int, default=3)
@@ -454,6 +631,8 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py measures on the GPU; none is visible")
+    if a.kv_dtype == "fp8":
+        return main_fp8kv(a)
     if a.graph:
         return main_graph(a)
     if a.ragged:
