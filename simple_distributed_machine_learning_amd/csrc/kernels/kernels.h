@@ -653,8 +653,24 @@ struct SampleStepArgs {
   int* gen_len = nullptr;
   int64_t eos = -1, pad = 0;
   void* thr_out = nullptr;
+  // The variant of sample_penalty.hip (ops/reference.py process_logits is the rule): any of the three being on moves
+  // the launch there, all off launches the kernel above. Row r's history is out[r][0 .. min(max(pos[r], 0), W)).
+  //   * pen_neg = fp32(theta), pen_pos = fp32(1 / theta): a logit whose token occurs in the history is multiplied by
+  //     pen_neg where it is negative, else by pen_pos, and rounded to bf16 (nearest even). Both 1: off.
+  //   * ngram = n in 1..kSampleMaxNgram: the tokens that followed an earlier occurrence of the history's last n - 1
+  //     tokens (n = 1: every token of the history) draw a logit of -inf. 0: off.
+  //   * logp [rows][ld_logp] fp32, out's shape: logp[r][pos[r]] = l_tok - logsumexp of the raw row, written where out
+  //     is. nullptr: off.
+  // A penalty or a ban needs out and vocab <= kSamplePenaltyMaxVocab (two bitmaps of vocab bits in LDS); logp needs out.
+  float pen_neg = 1.f, pen_pos = 1.f;
+  int ngram = 0;
+  float* logp = nullptr;
+  long ld_logp = 0;
 };
+constexpr int kSamplePenaltyMaxVocab = 65536;
+constexpr int kSampleMaxNgram = 8;
 void sample_step_bf16(const SampleStepArgs& a, hipStream_t stream);
+void sample_step_penalty_bf16(const SampleStepArgs& a, hipStream_t stream);  // sample_step_bf16 dispatches here
 // out[r] = bf16(wte[tok[r]] + wpe[pos[r]])  (C % 4 == 0; wte [V][C], wpe [P][C]; pos int32 on the device)
 void embedding_at_bf16(const int64_t* tok, const int* pos, const void* wte, const void* wpe, void* out, int rows, int C,
                        int V, int P, hipStream_t stream);

@@ -2491,10 +2491,13 @@ static sdml::SampleStepArgs sample_step_args(const char* who, const torch::Tenso
 
 // sample_logits with top-p, and the generation step's bookkeeping in the same launch (kernels.h SampleStepArgs).
 // out: int64 [B, W] (unit column stride); done, gen_len: int32 [B]. Returns the step's tokens [B].
+// repetition_penalty != 1, no_repeat_ngram_size > 0 or logp (fp32, out's shape) launch the variant of
+// sample_penalty.hip on the row's history out[row, :pos]; they are checked before anything is written.
 torch::Tensor sample_step(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, double top_p,
                           int64_t seed, int64_t sample0, torch::Tensor pos, c10::optional<torch::Tensor> out,
                           c10::optional<torch::Tensor> done, c10::optional<torch::Tensor> gen_len, int64_t eos,
-                          int64_t pad, int64_t rows_per_sample) {
+                          int64_t pad, int64_t rows_per_sample, double repetition_penalty,
+                          int64_t no_repeat_ngram_size, c10::optional<torch::Tensor> logp) {
   auto a = sample_step_args("sample_step", logits, vocab, temperature, top_k, top_p, seed, sample0, pos);
   TORCH_CHECK(rows_per_sample >= 1 && rows_per_sample <= INT_MAX, "sample_step: rows_per_sample must be >= 1");
   a.rows_per_sample = (int)rows_per_sample;
@@ -2517,6 +2520,29 @@ torch::Tensor sample_step(torch::Tensor logits, int64_t vocab, double temperatur
   if (done) a.done = done->data_ptr<int>();
   if (gen_len) a.gen_len = gen_len->data_ptr<int>();
   a.eos = eos, a.pad = pad;
+  TORCH_CHECK(std::isfinite(repetition_penalty) && repetition_penalty > 0.0,
+              "sample_step: repetition_penalty must be finite and > 0, got ", repetition_penalty);
+  a.pen_neg = (float)repetition_penalty, a.pen_pos = (float)(1.0 / repetition_penalty);
+  TORCH_CHECK(a.pen_neg > 0.f && std::isfinite(a.pen_neg) && a.pen_pos > 0.f && std::isfinite(a.pen_pos),
+              "sample_step: repetition_penalty ", repetition_penalty, " or its inverse leaves fp32's range");
+  TORCH_CHECK(no_repeat_ngram_size >= 0 && no_repeat_ngram_size <= sdml::kSampleMaxNgram,
+              "sample_step: no_repeat_ngram_size must be in 0..", sdml::kSampleMaxNgram, ", got ", no_repeat_ngram_size);
+  a.ngram = (int)no_repeat_ngram_size;
+  if (a.pen_neg != 1.f || a.pen_pos != 1.f || a.ngram > 0) {
+    TORCH_CHECK(out.has_value(), "sample_step: a repetition penalty or an n-gram ban reads the row's history: out "
+                                 "(with the positions) is required");
+    TORCH_CHECK(vocab <= sdml::kSamplePenaltyMaxVocab, "sample_step: a repetition penalty or an n-gram ban takes a "
+                "vocabulary of at most ", sdml::kSamplePenaltyMaxVocab, " (two bitmaps of vocab bits in LDS), got ",
+                vocab);
+  }
+  if (logp) {
+    TORCH_CHECK(out.has_value() && logp->is_cuda() && logp->device() == logits.device() &&
+                    logp->scalar_type() == torch::kFloat32 && logp->dim() == 2 && logp->sizes() == out->sizes() &&
+                    logp->stride(1) == 1 && (B <= 1 || logp->stride(0) >= logp->size(1)),
+                "sample_step: logp must be an fp32 device tensor of out's shape [B, W] with unit column stride");
+    a.logp = logp->data_ptr<float>();
+    a.ld_logp = B > 1 ? (long)logp->stride(0) : (long)logp->size(1);
+  }
   auto tokens = torch::empty({B}, logits.options().dtype(torch::kInt64));
   a.tokens = tokens.data_ptr<int64_t>();
   sdml::sample_step_bf16(a, cur_stream());
@@ -2714,7 +2740,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
         py::arg("seed"), py::arg("sample0"), py::arg("pos"), py::arg("out") = py::none(),
         py::arg("done") = py::none(), py::arg("gen_len") = py::none(), py::arg("eos") = -1, py::arg("pad") = 0,
-        py::arg("rows_per_sample") = 1);
+        py::arg("rows_per_sample") = 1, py::arg("repetition_penalty") = 1.0, py::arg("no_repeat_ngram_size") = 0,
+        py::arg("logp") = py::none());
   m.def("top_p_threshold", &top_p_threshold, "the candidate threshold of sample_step as a logit value, bf16 [B]",
         py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"));
   m.def("embedding_at", &embedding_at, "wte[tok[b]] + wpe[pos[b]] (bf16)");

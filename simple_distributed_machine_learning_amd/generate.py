@@ -18,7 +18,10 @@ then counts verify steps. ``--num_samples N`` prints N continuations of every pr
 first (one rank; the prompt is prefilled and its keys are stored once). ``--metrics`` gets one ``generate`` event: the
 tokens really generated over all rows, seconds, tokens/s, graph, lookup, lookup_ngram, steps, tokens per step and
 num_samples. ``--kv_dtype fp8`` keeps the KV cache as e4m3 bytes with one exponent per row (half the bytes a decode
-step streams; the plain loop and ``--graph`` only); the event carries ``kv_dtype``.
+step streams; the plain loop and ``--graph`` only); the event carries ``kv_dtype``. ``--repetition_penalty THETA``
+and ``--no_repeat_ngram_size N`` make the sampler read the row's own history (parallel/generate.py; not with ``--lookup``
+or ``--num_beams``); ``--logprobs`` prints `` logprob=<sum>`` after a row's tokens, the model's log-probability of what
+the row generated. The event carries the two knobs.
 """
 from __future__ import annotations
 
@@ -99,6 +102,14 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"],
                    help="the KV cache's storage: fp8 is e4m3 bytes with one int8 exponent per row, 66 bytes for 128 "
                         "(not with --lookup, --num_samples, --num_beams or --prefill_chunk)")
+    s.add_argument("--repetition_penalty", type=float, default=1.0, metavar="THETA",
+                   help="scale the logits of the tokens a row already holds: times THETA where negative, divided by "
+                        "it otherwise (1: off; not with --lookup or --num_beams)")
+    s.add_argument("--no_repeat_ngram_size", type=int, default=0, metavar="N",
+                   help="never draw a token that would repeat an N-gram of the row (0: off, at most 8; not with "
+                        "--lookup or --num_beams)")
+    s.add_argument("--logprobs", action="store_true",
+                   help="print each row's summed log-probability after its tokens (not with --lookup or --num_beams)")
     return p
 
 
@@ -173,8 +184,11 @@ def run(args) -> dict:
                        return_lengths=True, graph=args.graph, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
                        return_stats=not args.graph, prefill_chunk=args.prefill_chunk, num_samples=args.num_samples,
                        num_beams=args.num_beams, length_penalty=args.length_penalty,
-                       return_beams=args.return_beams and args.num_beams > 1, kv_dtype=args.kv_dtype)
+                       return_beams=args.return_beams and args.num_beams > 1, kv_dtype=args.kv_dtype,
+                       repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
+                       return_logprobs=args.logprobs)
         out, lengths = res[0], res[1]
+        scores = res[-1].sum(1).cpu().tolist() if args.logprobs else None
         steps = res[2]["steps"] if len(res) > 2 and isinstance(res[2], dict) else None
         rows = out.cpu().tolist()  # (the read-back ends the timed region)
         lengths = lengths.cpu().tolist()
@@ -189,13 +203,14 @@ def run(args) -> dict:
         (args.num_beams if beams and args.return_beams else 1)
     n_new = sum(lengths) - n_prompt  # the tokens really generated (the eos included), over all rows
     if mesh.is_master():
-        for r in rows:
-            print(",".join(str(t) for t in r), flush=True)
+        for i, r in enumerate(rows):
+            print(",".join(str(t) for t in r) + (f" logprob={scores[i]:.6f}" if scores else ""), flush=True)
         metrics.log(event="generate", samples=len(rows), prompt_len=prompts.shape[1], tokens=n_new, seconds=dt_s,
                     tokens_per_s=n_new / max(dt_s, 1e-9), temperature=args.temperature, top_k=args.top_k,
                     top_p=args.top_p, graph=bool(args.graph), lookup=args.lookup, lookup_ngram=args.lookup_ngram,
                     steps=steps, tokens_per_step=None if not steps else n_new / steps,
-                    num_samples=args.num_samples, num_beams=args.num_beams, kv_dtype=args.kv_dtype)
+                    num_samples=args.num_samples, num_beams=args.num_beams, kv_dtype=args.kv_dtype,
+                    repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size)
     return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
 
 

@@ -497,18 +497,33 @@ def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int,
 
 
 def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float, seed: int, sample0: int, positions,
-                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0, rows_per_sample: int = 1):
+                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0, rows_per_sample: int = 1,
+                repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, logp=None):
     """sample_logits over the top-p nucleus of the top-k candidates, with one generation step's bookkeeping in the
     same launch (ops/reference.py sample_step is the definition): tokens int64 [B]; ``out`` int64 [B, W] gets the token
     at column positions[row], ``gen_len`` int32 [B] grows by one, ``done`` int32 [B] is set on ``eos`` (-1: none); a
     row already done emits ``pad`` and changes nothing. ``rows_per_sample``: row r is sample sample0 + r //
-    rows_per_sample (the verify step of prompt-lookup speculation draws several positions of a sample at once). ROCm
-    bf16: the on-device sampler, no host synchronisation."""
+    rows_per_sample (the verify step of prompt-lookup speculation draws several positions of a sample at once).
+    ``repetition_penalty`` theta != 1 and ``no_repeat_ngram_size`` n in 1..8: the token is drawn from
+    ``process_logits`` (ops/reference.py) of the row and its history out[row, :positions[row]]; ``logp`` fp32 [B, W]
+    gets the raw row's log-probability of the token where ``out`` gets the token. Still one launch (the variant of
+    csrc/kernels/sample_penalty.hip, vocab <= 65536 with a penalty or a ban); with the three off it is the call it
+    always was. ROCm bf16: the on-device sampler, no host synchronisation."""
     if int(rows_per_sample) < 1:
         raise ValueError(f"sample_step: rows_per_sample must be >= 1, got {rows_per_sample}")
+    extra = float(repetition_penalty) != 1.0 or no_repeat_ngram_size != 0 or logp is not None
     if _hip_bf16(logits):
-        return kernels().sample_step(logits, int(vocab), float(temperature), int(top_k), float(top_p), int(seed),
-                                     int(sample0), positions, out, done, gen_len, int(eos), int(pad),
-                                     int(rows_per_sample))
+        args = (logits, int(vocab), float(temperature), int(top_k), float(top_p), int(seed), int(sample0), positions,
+                out, done, gen_len, int(eos), int(pad), int(rows_per_sample))
+        if not extra:
+            return kernels().sample_step(*args)
+        _ref.check_penalty("sample_step", repetition_penalty, no_repeat_ngram_size)
+        try:
+            return kernels().sample_step(*args, float(repetition_penalty), int(no_repeat_ngram_size), logp)
+        except RuntimeError as e:
+            _beam_kernel_error(e, "sample_step")
+    if not extra:
+        return _ref.sample_step(logits, vocab, temperature, top_k, top_p, seed, sample0, positions, out, done, gen_len,
+                                eos, pad, int(rows_per_sample))
     return _ref.sample_step(logits, vocab, temperature, top_k, top_p, seed, sample0, positions, out, done, gen_len,
-                            eos, pad, int(rows_per_sample))
+                            eos, pad, int(rows_per_sample), repetition_penalty, no_repeat_ngram_size, logp)

@@ -388,17 +388,74 @@ def sample_logits(logits, vocab: int, temperature: float, top_k: int, seed: int,
     return _first_argmax(zf * inv_t + g, cand)
 
 
+SAMPLE_MAX_NGRAM = 8  # csrc/kernels/kernels.h kSampleMaxNgram
+
+
+def check_penalty(who: str, repetition_penalty, no_repeat_ngram_size):
+    """The refusals of the two knobs, shared by the op and the drivers."""
+    th = float(repetition_penalty)
+    if not (math.isfinite(th) and th > 0):
+        raise ValueError(f"{who}: repetition_penalty must be finite and > 0 (1: off), got {repetition_penalty!r}")
+    n = no_repeat_ngram_size
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= SAMPLE_MAX_NGRAM:
+        raise ValueError(f"{who}: no_repeat_ngram_size must be an integer in 0..{SAMPLE_MAX_NGRAM} (0: off), got {n!r}")
+
+
+def process_logits(logits, vocab: int, out, positions, repetition_penalty: float = 1.0,
+                   no_repeat_ngram_size: int = 0):
+    """The logits the penalised sampler draws from: bf16-valued [B, ld] like ``logits``, row by row on the row's
+    history hist = out[row, 0:pos], pos = positions[row] clamped to [0, W] (the prompt and what was generated so far,
+    without the column about to be written); history tokens outside [0, vocab) have no logit and are skipped.
+
+    Repetition penalty theta > 0 (1: off): every v < vocab that occurs in hist gets l'_v = bf16_rn(fp32(l_v) * f), f =
+    fp32(theta) where l_v < 0, else fp32(1 / theta) (the inverse taken in double): one fp32 multiply, one rounding to
+    nearest even. -0, NaN and +-inf follow from the multiply. N-gram ban n (0: off), after the penalty: with m = n - 1,
+    every start s with s + m < pos and hist[s:s+m] == hist[pos-m:pos] bans hist[s+m] (n = 1: every token of hist);
+    nothing is banned while pos < n; a banned logit is -inf. Columns >= vocab are copied."""
+    check_penalty("process_logits", repetition_penalty, no_repeat_ngram_size)
+    th, n = float(repetition_penalty), int(no_repeat_ngram_size)
+    res = logits.clone()
+    f_neg = torch.tensor(th, dtype=torch.float32, device=logits.device)
+    f_pos = torch.tensor(1.0 / th, dtype=torch.float32, device=logits.device)
+    W = out.shape[1]
+    for r, pos in enumerate(positions.tolist()):
+        hist = out[r, :min(max(int(pos), 0), W)]
+        h = hist.shape[0]
+        ok = (hist >= 0) & (hist < vocab)
+        if float(f_neg) != 1.0 or float(f_pos) != 1.0:
+            seen = hist[ok].unique()
+            l = res[r, seen].float()
+            res[r, seen] = (l * torch.where(l < 0, f_neg, f_pos)).to(res.dtype)
+        if n > 0 and h >= n:
+            m = n - 1
+            hit = (hist.unfold(0, m, 1)[:h - m] == hist[h - m:]).all(1) if m else torch.ones(h, dtype=torch.bool)
+            res[r, hist[m:][hit.to(hist.device) & ok[m:]]] = -math.inf
+    return res
+
+
 def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float, seed: int, sample0: int, positions,
-                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0, rows_per_sample: int = 1):
+                out=None, done=None, gen_len=None, eos: int = -1, pad: int = 0, rows_per_sample: int = 1,
+                repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, logp=None):
     """sample_logits over the nucleus (top_p_candidates) plus one generation step's bookkeeping, in place. Returns the
     step's tokens [B]. Per row, with pos = positions[row]: a row whose ``done`` flag is set emits ``pad`` and changes
     nothing; else the token goes to out[row, pos], gen_len[row] grows by one and done[row] is set when the token is
     ``eos`` (-1: none). A pos outside [0, W) changes none of the three. With top_p off and no bookkeeping tensors the
-    tokens are sample_logits'."""
+    tokens are sample_logits'. ``repetition_penalty`` != 1 or ``no_repeat_ngram_size`` > 0: the token is drawn from
+    ``process_logits`` of the row (``out`` is then required). ``logp`` fp32 [B, W] (with ``out``): where the token is
+    written, logp[row, pos] = l_tok - logsumexp_{v < vocab} l_v of the RAW logits in fp32 (a NaN counts as -inf)."""
     if temperature < 0:
         raise ValueError(f"temperature must be >= 0, got {temperature}")
     if not 0.0 <= top_p <= 1.0:
         raise ValueError(f"top_p must be in [0, 1], got {top_p}")
+    check_penalty("sample_step", repetition_penalty, no_repeat_ngram_size)
+    raw = logits
+    if float(repetition_penalty) != 1.0 or no_repeat_ngram_size > 0:
+        if out is None:
+            raise ValueError("sample_step: a repetition penalty or an n-gram ban reads the row's history: out (with "
+                             "the positions) is required")
+        logits = process_logits(logits, vocab, out, positions, repetition_penalty, no_repeat_ngram_size)
+    if logp is not None and (out is None or logp.dtype != torch.float32 or logp.shape != out.shape):
+        raise ValueError("sample_step: logp must be an fp32 tensor of out's shape [B, W]")
     z = logits[:, :vocab]
     cand = top_p_candidates(z, top_k, top_p, temperature)
     zf = torch.nan_to_num(z.float(), nan=-math.inf)
@@ -418,6 +475,14 @@ def sample_step(logits, vocab: int, temperature: float, top_k: int, top_p: float
     if out is not None:
         rows = torch.arange(B, device=z.device)[write]
         out[rows, pos[write]] = tok[write]
+        if logp is not None:
+            zr = raw[:, :vocab].float()
+            zr = torch.where(torch.isnan(zr), torch.full_like(zr, -math.inf), zr)
+            m = zr.max(dim=1).values
+            m0 = torch.where(m > -math.inf, m, torch.zeros_like(m))
+            lse = m0 + torch.log(torch.exp(zr - m0[:, None]).sum(dim=1))
+            l_tok = raw[:, :vocab].float().gather(1, tok[:, None])[:, 0]
+            logp[rows, pos[write]] = (l_tok - lse)[write]
     if gen_len is not None:
         gen_len += write.to(gen_len.dtype)
     if done is not None:

@@ -17,7 +17,8 @@ tokens and lengths are those of the eager call bit for bit.
 
 A session (the static token / out / done / length buffers, the KV caches with their counters, the graph) stays on the
 engine as ``engine.decode_session``; at most one. The next call with the same key, (B, total width, temperature,
-top_k, top_p, seed, sample0, eos, pad, kv_dtype, the parameters' storage addresses),
+top_k, top_p, seed, sample0, eos, pad, repetition_penalty, no_repeat_ngram_size, logprobs, kv_dtype, the parameters'
+storage addresses),
 replays it without capturing again; any
 other key replaces it. The weights are read in place, so optimizer steps between two calls need no new capture as long
 as the storages stay. ``engine.decode_graph_captures`` counts the captures.
@@ -51,7 +52,7 @@ def check_graph(engine, cfg) -> None:
 class DecodeSession:
     """The static state of one captured decode step; see the module docstring."""
 
-    def __init__(self, engine, key, B: int, total: int, _sites=None, kv_dtype: str = "bf16"):
+    def __init__(self, engine, key, B: int, total: int, _sites=None, kv_dtype: str = "bf16", logprobs: bool = False):
         """``_sites`` (tools/bench_generate.py only): the call sites on one launch, None: models/gpt2.py's."""
         dev = engine.device
         self.key, self.B, self.total, self._sites = key, B, total, _sites
@@ -62,6 +63,7 @@ class DecodeSession:
         self.out = torch.zeros((B, total), dtype=torch.int64, device=dev)
         self.done = torch.zeros(B, dtype=torch.int32, device=dev)
         self.gen_len = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.logp = torch.zeros((B, total), dtype=torch.float32, device=dev) if logprobs else None  # beside out
         self.graph = None
 
     def step(self, engine, sampling: Sampling) -> None:
@@ -94,6 +96,8 @@ class DecodeSession:
             c.lens.zero_()
         self.done.zero_()
         self.gen_len.zero_()
+        if self.logp is not None:
+            self.logp.zero_()
 
     def replay(self) -> None:
         self.graph.replay()
@@ -119,7 +123,7 @@ def generate_graphed(engine, prompts, lens_host, new: int, sampling: Sampling, c
         if ses is None or ses.key != key:
             engine.decode_session = None  # (the old session's memory goes before the new one's is taken)
             del ses
-            ses = DecodeSession(engine, key, B, total, kv_dtype=kv_dtype)
+            ses = DecodeSession(engine, key, B, total, kv_dtype=kv_dtype, logprobs=sp.logprobs)
             ses.capture(engine, sp)
             engine.decode_session = ses
         ses.reset()

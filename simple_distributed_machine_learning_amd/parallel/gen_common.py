@@ -23,7 +23,9 @@ def eval_stages(modules):
 
 @dataclass(frozen=True)
 class Sampling:
-    """The sampler's arguments of one call, checked: ``seed`` is through ``dropout_seed``, ``eos`` is -1 for none."""
+    """The sampler's arguments of one call, checked: ``seed`` is through ``dropout_seed``, ``eos`` is -1 for none.
+    ``repetition_penalty`` (1: off), ``no_repeat_ngram_size`` (0: off) and ``logprobs`` are the step sampler's knobs
+    (ops/reference.py process_logits); ``extra``: one of them is on."""
     vocab: int
     temperature: float
     top_k: int
@@ -32,9 +34,23 @@ class Sampling:
     sample0: int
     eos: int
     pad: int
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    logprobs: bool = False
+
+    @property
+    def extra(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0 or self.logprobs
 
     def step(self, logits, positions, state):
-        """``sample_step`` with its bookkeeping on ``state`` (anything with ``out``, ``done`` and ``gen_len``)."""
+        """``sample_step`` with its bookkeeping on ``state`` (anything with ``out``, ``done`` and ``gen_len``, and
+        with ``logp`` where ``logprobs`` is on)."""
+        if self.extra:
+            return sample_step(logits, self.vocab, self.temperature, self.top_k, self.top_p, self.seed, self.sample0,
+                               positions, state.out, state.done, state.gen_len, self.eos, self.pad,
+                               repetition_penalty=self.repetition_penalty,
+                               no_repeat_ngram_size=self.no_repeat_ngram_size,
+                               logp=state.logp if self.logprobs else None)
         return sample_step(logits, self.vocab, self.temperature, self.top_k, self.top_p, self.seed, self.sample0,
                            positions, state.out, state.done, state.gen_len, self.eos, self.pad)
 
@@ -58,10 +74,11 @@ class TokenState:
     [R, total] and ``lens0`` int64 [R] hold the R = B ``repeat`` rows, every prompt's ``repeat`` times in a row.
     ``stepped``: ``out`` starts as the pad token and the cleaned prompts, and ``sample_step`` writes it, counts in
     ``gen_len`` and sets ``done`` (int32 [R]); otherwise the host stores a column per step, every row ends at ``total``
-    and there are no counters. ``storage`` = (out, done, gen_len): a graph session's static buffers, not new ones."""
+    and there are no counters. ``storage`` = (out, done, gen_len): a graph session's static buffers, not new ones.
+    ``logprobs``: ``logp`` fp32 [R, total], zeros for the step sampler to write (else None)."""
 
     def __init__(self, prompts, lens_host, total: int, pad: int, device, stepped: bool = True, repeat: int = 1,
-                 storage=None):
+                 storage=None, logprobs: bool = False):
         B, S0 = prompts.shape
         R = B * repeat
         self.stepped, self.total = stepped, total
@@ -72,6 +89,7 @@ class TokenState:
             storage = (torch.empty((R, total), dtype=torch.int64, device=device),
                        *(torch.zeros((2, R), dtype=torch.int32, device=device) if stepped else (None, None)))
         self.out, self.done, self.gen_len = storage
+        self.logp = torch.zeros((R, total), dtype=torch.float32, device=device) if logprobs else None
         if stepped:
             self.out.fill_(pad)
             self.prompts = clean_prompts(self.prompts, self.lens0, self.out[:B, :S0])
@@ -108,13 +126,15 @@ def decode_loop(logits, new: int, check: int, sample, advance, all_done) -> int:
     return t + 1
 
 
-def result(out, lengths, lens0, return_lengths: bool, return_stats: bool, steps: int, row_steps=None):
+def result(out, lengths, lens0, return_lengths: bool, return_stats: bool, steps: int, row_steps=None, logp=None):
     """generate()'s result: tokens, (tokens, lengths), (tokens, stats) or (tokens, lengths, stats). ``row_steps``
-    None: a row emits one token in every step it takes part in."""
+    None: a row emits one token in every step it takes part in. ``logp``: appended to the result."""
     res = (out, lengths) if return_lengths else out
     if return_stats:
         generated = lengths - lens0
         stats = {"steps": steps, "row_steps": generated.clone() if row_steps is None else row_steps.to(torch.int64),
                  "generated": generated}
         res = (res if isinstance(res, tuple) else (res,)) + (stats,)
+    if logp is not None:
+        res = (res if isinstance(res, tuple) else (res,)) + (logp,)
     return res

@@ -71,6 +71,18 @@ depend on the batch, and ``graph=True`` replays them bit for bit. It serves the 
 eos, top-k, top-p) and ``graph=True``; it is refused with ``lookup > 0``, ``num_samples > 1``, ``num_beams > 1``,
 ``prefill_chunk > 0`` and by ``GenerationSession``. ``"bf16"`` (the default) runs the lines it always ran.
 
+``repetition_penalty``, ``no_repeat_ngram_size`` and ``return_logprobs`` move the step onto ``sample_step`` as well,
+on its variant that reads the row's own history out[row, :pos] in the same launch (ops/reference.py
+``process_logits`` is the rule; csrc/kernels/sample_penalty.hip): a logit whose token occurs in the history is
+multiplied by theta where negative and by 1 / theta otherwise and rounded to bf16 again, then every token that would
+complete an n-gram the history already holds gets -inf, and temperature, top-k, top-p and the noise work on that row
+unchanged. The log-probability is that of the raw logits (no penalty, temperature 1) for the token the row emits:
+what the model thought of it, whatever the knobs; ``logprobs.sum(1)`` ranks the rows of ``num_samples``. A step is
+still one sampler launch and reads nothing back, so every driver that samples through ``Sampling.step`` serves them:
+the plain loop at any pp, ``graph=True``, ``num_samples``, ``prefill_chunk`` and ``GenerationSession``. Refused with
+``lookup > 0`` (a verify row's history would have to include the step's own drafts) and ``num_beams > 1``; on the
+kernels a penalty or a ban takes a vocabulary of at most 65536.
+
 Limitations: tensor parallelism, data parallelism and ``--schedule rotate`` are refused. With pp ranks one rank works
 at a time (a token must leave the last stage before stage 0 can embed it); several sample groups in flight would fill
 the bubble and are not implemented. ``graph=True`` is refused with pp > 1: the step's boundaries cross ranks between
@@ -93,6 +105,7 @@ import torch
 from ..ops.decode import (ATTENTION_FORK_MAX_N, BEAM_MAX_K, BEAM_MAX_ROWS, BEAM_MAX_VOCAB, KV_DTYPES,
                           LINEAR_DECODE_MAX_M, LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM, beam_backtrack, beam_step,
                           lookup_step)
+from ..ops.reference import check_penalty
 from .decode_graph import check_graph, generate_graphed
 from .gen_common import Sampling, TokenState, decode_loop, eval_stages, result
 from .session import GenerationSession
@@ -196,8 +209,9 @@ def _generate_chunked(engine, prompts, lens_host, new: int, sp: Sampling, check:
     s = GenerationSession(engine, prompts, prompts.shape[1] + new, lens_host, sp.pad, sample0=sp.sample0)
     lens0 = s.lengths.to(torch.int64)
     out, lengths = s.run(new, sp, check, prefill_chunk)
+    logp = s.logp
     s.close()
-    return out, lengths, lens0, s.steps
+    return (out, lengths, lens0, s.steps), logp
 
 
 def _check_samples(engine, num_samples, graph: bool, lookup: int, prefill_chunk: int):
@@ -357,6 +371,20 @@ def _check_kv_dtype(kv_dtype, lookup: int, num_samples: int, num_beams: int, pre
             raise ValueError(f"generate: kv_dtype={kv_dtype!r} is not supported with {what}")
 
 
+def _check_penalty(repetition_penalty, no_repeat_ngram_size, return_logprobs, lookup: int = 0, num_beams: int = 1):
+    """The refusals of ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``return_logprobs``; returns the three as
+    ``Sampling``'s last fields."""
+    check_penalty("generate", repetition_penalty, no_repeat_ngram_size)
+    sp3 = float(repetition_penalty), int(no_repeat_ngram_size), bool(return_logprobs)
+    if sp3 != (1.0, 0, False):
+        for on, what in ((lookup > 0, "lookup > 0 (a verify row's history would have to hold the step's own drafts)"),
+                         (num_beams > 1, "num_beams > 1 (the beam step ranks by its own scores)")):
+            if on:
+                raise ValueError("generate: repetition_penalty, no_repeat_ngram_size and return_logprobs are not "
+                                 f"supported with {what}")
+    return sp3
+
+
 def _generate_pipeline(engine, cfg, st: TokenState, sp: Sampling, new: int, check: int, kv_dtype: str = "bf16"):
     """The plain driver, on every rank of the pipeline (module docstring)."""
     mesh, dev, P = engine.mesh, engine.device, engine.P
@@ -437,6 +465,8 @@ def _generate_pipeline(engine, cfg, st: TokenState, sp: Sampling, new: int, chec
                     torch.zeros((B, total + 1), dtype=torch.int64, device=dev)
                 tr.all_reduce(buf, channel="fwd", async_op=False)
                 out, lengths = buf[:, :total].contiguous(), buf[:, total].clone()
+                if st.logp is not None:  # (zeros on every rank but the last stage's)
+                    tr.all_reduce(st.logp, channel="fwd", async_op=False)
     return out, lengths, st.lens0, steps
 
 
@@ -446,7 +476,8 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
              eos_token: Optional[int] = None, pad_token: int = 0, stop_check: int = 16, return_lengths: bool = False,
              graph: bool = False, lookup: int = 0, lookup_ngram: int = 2, return_stats: bool = False,
              prefill_chunk: int = 0, num_samples: int = 1, num_beams: int = 1, length_penalty: float = 0.0,
-             return_beams: bool = False, kv_dtype: str = "bf16"):
+             return_beams: bool = False, kv_dtype: str = "bf16", repetition_penalty: float = 1.0,
+             no_repeat_ngram_size: int = 0, return_logprobs: bool = False):
     """Tokens [B, S0 + max_new_tokens] (int64, on the engine's device) on every rank; see the module docstring.
     ``seed``: the run seed of the noise (None: 0); ``temperature`` 0 is greedy and draws no noise; ``top_p`` in (0, 1)
     samples inside the nucleus of the top-k candidates. ``prompt_lens`` [B] with right-padded ``prompts`` (see
@@ -470,7 +501,11 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     ``prefill_chunk``): beam search (module docstring). The result is each prompt's best hypothesis under
     ``score / length ** length_penalty``; ``return_beams``: all [B K, ...] rows, best first per prompt, and their
     scores fp32 [B K] appended to the result; 1 runs the lines it always ran. ``kv_dtype`` "fp8": an 8-bit KV cache
-    (module docstring; the plain loop and ``graph=True`` only); "bf16" runs the lines it always ran."""
+    (module docstring; the plain loop and ``graph=True`` only); "bf16" runs the lines it always ran.
+    ``repetition_penalty`` theta > 0 (1: off), ``no_repeat_ngram_size`` n in 0..8 (0: off): the step sampler draws
+    from ``process_logits`` of a row's logits and its own history (module docstring). ``return_logprobs``: fp32
+    [R, total] is appended to the result, the model's log-probability of every generated token at its column, 0 at
+    prompt and pad columns. Not with ``lookup > 0`` or ``num_beams > 1``; all three off runs the lines it always ran."""
     from ..models.gpt2 import dropout_seed
 
     new = int(max_new_tokens)
@@ -491,11 +526,14 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     if graph:
         check_graph(engine, cfg)
     sp = Sampling(cfg.vocab_size, temperature, top_k, top_p, dropout_seed(0 if seed is None else seed), sample0,
-                  -1 if eos_token is None else int(eos_token), int(pad_token))
+                  -1 if eos_token is None else int(eos_token), int(pad_token),
+                  *_check_penalty(repetition_penalty, no_repeat_ngram_size, return_logprobs, lookup, num_beams))
     check = int(stop_check) if eos_token is not None else 0
     # the step kernel (sample + bookkeeping in one launch) serves these arguments; without them the host stores a column
-    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0
-    state = partial(TokenState, prompts, lens_host, prompts.shape[1] + new, sp.pad, engine.device)
+    stepped = lens_host is not None or eos_token is not None or 0.0 < float(top_p) < 1.0 or sp.extra
+    state = partial(TokenState, prompts, lens_host, prompts.shape[1] + new, sp.pad, engine.device,
+                    logprobs=sp.logprobs)
+    logp = None
     if num_beams > 1:
         K = num_beams
         *res, scores = _generate_beam(engine, state(repeat=K), sp, new, check, K, float(length_penalty))
@@ -506,16 +544,19 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
             res = (res if isinstance(res, tuple) else (res,)) + (scores,)
         return res
     if prefill_chunk > 0:
-        res = _generate_chunked(engine, prompts, lens_host, new, sp, check, prefill_chunk)
-    elif new == 0:  # nothing to draw in any other mode: the prompts come back, cleaned where the mode steps
-        st = state(stepped=stepped or lookup > 0, repeat=num_samples)
-        res = st.out, st.lengths(), st.lens0, 0
-    elif num_samples > 1:
-        res = _generate_forked(engine, state(stepped=stepped, repeat=num_samples), sp, new, check, num_samples)
-    elif graph:
+        res, logp = _generate_chunked(engine, prompts, lens_host, new, sp, check, prefill_chunk)
+    elif graph and new > 0:
         res = generate_graphed(engine, prompts, lens_host, new, sp, check, kv_dtype)
-    elif lookup > 0:
+        logp = engine.decode_session.logp.clone() if sp.logprobs else None
+    elif lookup > 0 and new > 0:
         res = _generate_lookup(engine, state(), sp, new, int(stop_check), lookup, lookup_ngram)
     else:
-        res = _generate_pipeline(engine, cfg, state(stepped=stepped), sp, new, check, kv_dtype)
-    return result(*res[:3], return_lengths, return_stats, *res[3:])
+        st = state(stepped=stepped or lookup > 0, repeat=num_samples)
+        logp = st.logp
+        if new == 0:  # nothing to draw in any of these modes: the prompts come back, cleaned where the mode steps
+            res = st.out, st.lengths(), st.lens0, 0
+        elif num_samples > 1:
+            res = _generate_forked(engine, st, sp, new, check, num_samples)
+        else:
+            res = _generate_pipeline(engine, cfg, st, sp, new, check, kv_dtype)
+    return result(*res[:3], return_lengths, return_stats, *res[3:], logp=logp if sp.logprobs else None)

@@ -102,13 +102,14 @@ class GenerationSession:
         self.done = torch.zeros(B, dtype=torch.int32, device=dev)
         self.out = torch.full((B, max_len), self.pad_token, dtype=torch.int64, device=dev)
         self.out[:, :S0] = clean_prompts(prompts.to(dev), self.lengths, self.out[:, :S0])
+        self.logp = torch.zeros((B, max_len), dtype=torch.float32, device=dev)  # filled where a call asks for logprobs
         self.stages = [engine.stages[s] for s in range(engine.P)]
         self.caches = [m.new_cache(B, max_len) for m in self.stages]
         self.steps = 0  # decode loop steps of the last generate call
 
     def close(self):
         """Drop the caches and the token matrix; the session takes no further calls."""
-        self.caches = self.out = self.lengths = self.gen_len = self.done = None
+        self.caches = self.out = self.lengths = self.gen_len = self.done = self.logp = None
 
     def _open(self, what: str):
         if self.caches is None:
@@ -210,11 +211,15 @@ class GenerationSession:
         return logits
 
     def generate(self, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-                 eos_token: Optional[int] = None, stop_check: int = 16, prefill_chunk: int = 0):
+                 eos_token: Optional[int] = None, stop_check: int = 16, prefill_chunk: int = 0,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, return_logprobs: bool = False):
         """Up to ``max_new_tokens`` more tokens per row that is not done; returns (tokens int64 [B, max_len], lengths
         int64 [B]), copies of the session's state. The sampling arguments are ``generate()``'s. ``prefill_chunk`` = P
-        > 0: the catch-up always runs through ``extend``, at most P positions per row and pass."""
-        from .generate import _check_step
+        > 0: the catch-up always runs through ``extend``, at most P positions per row and pass. ``repetition_penalty``
+        / ``no_repeat_ngram_size``: ``generate()``'s, on everything the row holds (earlier calls and appended tokens
+        included). ``return_logprobs``: fp32 [B, max_len] is appended, the log-probability of every token drawn by the
+        calls that asked for it, 0 elsewhere."""
+        from .generate import _check_penalty, _check_step
 
         self._open("generate")
         new = int(max_new_tokens)
@@ -228,8 +233,10 @@ class GenerationSession:
                 raise ValueError(f"GenerationSession.generate: row {b} holds {self._len_h[b]} tokens; {new} more "
                                  f"would pass max_len={self.max_len}")
         sp = Sampling(self.cfg.vocab_size, temperature, top_k, top_p, self.seed, self.sample0,
-                      -1 if eos_token is None else int(eos_token), self.pad_token)
-        return self.run(new, sp, int(stop_check) if eos_token is not None else 0, int(prefill_chunk))
+                      -1 if eos_token is None else int(eos_token), self.pad_token,
+                      *_check_penalty(repetition_penalty, no_repeat_ngram_size, return_logprobs))
+        res = self.run(new, sp, int(stop_check) if eos_token is not None else 0, int(prefill_chunk))
+        return res + (self.logp.clone(),) if sp.logprobs else res
 
     @torch.no_grad()
     def run(self, new: int, sp: Sampling, check: int, prefill_chunk: int):
