@@ -625,6 +625,23 @@ int linear_decode_splits(int N, int K);
 size_t linear_decode_workspace_floats(int M, int N, int K);
 void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y, float* ws, int M, int N, int K,
                         int ldx, int ldw, int epi, hipStream_t stream, int* tickets = nullptr);
+// y [M][N] bf16 = epilogue(ws[0] + ws[1] + ... + ws[KS - 1]) for fp32 slabs ws [KS][M][N], summed in split order:
+// the second launch of linear_decode_bf16, shared with linear_rows_bf16 (M * N % 4 == 0).
+void linear_splits_reduce_bf16(const float* ws, const void* bias, void* y, int M, int N, int KS, int epi,
+                               hipStream_t stream);
+// linear_decode_bf16's product for kLinearDecodeMaxM < M <= kLinearRowsMaxM rows (linear_rows.hip): 64-row panels of x
+// staged in LDS against W fragments in VGPRs, a workgroup per (panel, column tile, K split). Row m has the bits
+// linear_decode_bf16 gives that row in a call of at most 64 rows: the same MFMA chains over the same k ranges
+// (linear_decode_splits and its wave ranges), summed in the same order, and the same epilogue. Operand rules as
+// linear_decode_bf16, and M * ldx * 2 < 2^31. ws: linear_rows_workspace_floats(M, N, K) fp32 (0: none). No atomics.
+// kLinearRowsDispatchM: the rows up to which ops/decode.py sends a call here and not to gemm_bf16 (measured,
+// README.md "linear_rows").
+constexpr int kLinearRowsMaxM = 512;
+constexpr int kLinearRowsDispatchM = 512;
+bool linear_rows_supported(int M, int N, int K, int ldx, int ldw);
+size_t linear_rows_workspace_floats(int M, int N, int K);
+void linear_rows_bf16(const void* x, const void* w, const void* bias, void* y, float* ws, int M, int N, int K, int ldx,
+                      int ldw, int epi, hipStream_t stream);
 // out[r] (int64) = the token of row r of bf16 logits [rows][ld] among columns < vocab: inv_temp == 0 greedy, else
 // Gumbel-max at 1 / T = inv_temp over the top_k candidates (top_k <= 0 or >= vocab: all), noise keyed by
 // (seed, sample0 + r / rows_per_sample, pos[r], token) (sample.hip). pos: int32 [rows] on the device.

@@ -24,9 +24,9 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
-#include "gelu.h"
 #include "handoff.h"
 #include "kernels.h"
+#include "linear_epi.h"
 
 namespace sdml {
 namespace {
@@ -36,12 +36,6 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MAXW = 4;  // waves per workgroup
-
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((unsigned)v) << 16); }
-__device__ __forceinline__ u16 f2bf(float f) {
-  __hip_bfloat16 h = __float2bfloat16(f);
-  return *reinterpret_cast<u16*>(&h);
-}
 
 struct LdParams {
   const u16* x;
@@ -54,12 +48,6 @@ struct LdParams {
   int KS, kb_per_split, waves;
   int epi;  // EPI_STORE, EPI_BIAS, EPI_BIAS_GELU
 };
-
-__device__ __forceinline__ u16 epilogue(float acc, const u16* bias, int n, int epi) {
-  if (epi == EPI_STORE) return f2bf(acc);
-  const u16 u = f2bf(acc + bf2f(bias[n]));
-  return epi == EPI_BIAS ? u : f2bf(gelu_f(bf2f(u)));
-}
 
 // grid (N / 16, KS); block 64 * waves. MG = ceil(M / 16) row groups. TK: the one-launch form (KS > 1 and tickets).
 template <int MG, bool TK>
@@ -115,7 +103,7 @@ __global__ void __launch_bounds__(64 * MAXW) linear_decode_kernel(LdParams p) {
     else if (p.KS > 1)
       p.ws[((int64_t)blockIdx.y * p.M + m) * p.N + n0 + n] = s;
     else
-      p.y[(int64_t)m * p.N + n0 + n] = epilogue(s, p.bias, n0 + n, p.epi);
+      p.y[(int64_t)m * p.N + n0 + n] = linear_epilogue(s, p.bias, n0 + n, p.epi);
   }
   if constexpr (TK) {
     // the slab went out write-through; draw a ticket on the tile (handoff.h). red is free after the barrier inside
@@ -143,14 +131,14 @@ __global__ void __launch_bounds__(64 * MAXW) linear_decode_kernel(LdParams p) {
       }
       typedef u16 u16x2 __attribute__((ext_vector_type(2)));
       u16x2 o;
-      o[0] = epilogue(s0, p.bias, n, p.epi), o[1] = epilogue(s1, p.bias, n + 1, p.epi);
+      o[0] = linear_epilogue(s0, p.bias, n, p.epi), o[1] = linear_epilogue(s1, p.bias, n + 1, p.epi);
       *reinterpret_cast<u16x2*>(p.y + i) = o;
     }
     if (threadIdx.x == 0) handoff::reset_ticket(p.tickets + blockIdx.x);
   }
 }
 
-// y = epilogue(sum over the splits in split order); 4 columns per thread
+// y = linear_epilogue(sum over the splits in split order); 4 columns per thread
 __global__ void __launch_bounds__(256) linear_decode_reduce_kernel(LdParams p) {
   const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)p.M * p.N;
@@ -162,7 +150,7 @@ __global__ void __launch_bounds__(256) linear_decode_reduce_kernel(LdParams p) {
   typedef u16 u16x4 __attribute__((ext_vector_type(4)));
   u16x4 o;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = epilogue(s[e], p.bias, n + e, p.epi);
+  for (int e = 0; e < 4; ++e) o[e] = linear_epilogue(s[e], p.bias, n + e, p.epi);
   reinterpret_cast<u16x4*>(p.y)[i4] = o;
 }
 
@@ -183,6 +171,17 @@ int linear_decode_splits(int N, int K) {
 size_t linear_decode_workspace_floats(int M, int N, int K) {
   const int ks = linear_decode_splits(N, K);
   return ks > 1 ? (size_t)ks * M * N : 0;
+}
+
+void linear_splits_reduce_bf16(const float* ws, const void* bias, void* y, int M, int N, int KS, int epi,
+                               hipStream_t stream) {
+  LdParams p{};
+  p.ws = const_cast<float*>(ws);
+  p.bias = static_cast<const u16*>(bias);
+  p.y = static_cast<u16*>(y);
+  p.M = M, p.N = N, p.KS = KS, p.epi = epi;
+  const int64_t n4 = (int64_t)M * N / 4;
+  hipLaunchKernelGGL(linear_decode_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, p);
 }
 
 void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y, float* ws, int M, int N, int K,
@@ -215,10 +214,7 @@ void linear_decode_bf16(const void* x, const void* w, const void* bias, void* y,
     case 3: hipLaunchKernelGGL((linear_decode_kernel<3, false>), grid, block, 0, stream, p); break;
     default: hipLaunchKernelGGL((linear_decode_kernel<4, false>), grid, block, 0, stream, p); break;
   }
-  if (p.KS > 1) {
-    const int64_t n4 = (int64_t)M * N / 4;
-    hipLaunchKernelGGL(linear_decode_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, p);
-  }
+  if (p.KS > 1) linear_splits_reduce_bf16(ws, bias, y, M, N, p.KS, epi, stream);
 }
 
 }  // namespace sdml

@@ -2436,6 +2436,40 @@ torch::Tensor linear_decode(torch::Tensor x, torch::Tensor w, c10::optional<torc
   return y;
 }
 
+bool linear_rows_supported_op(int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw) {
+  if (M > INT_MAX || N > INT_MAX || K > INT_MAX || ldx > INT_MAX || ldw > INT_MAX) return false;
+  return sdml::linear_rows_supported((int)M, (int)N, (int)K, (int)ldx, (int)ldw);
+}
+
+// linear_decode's product and bits per row for 64 < M <= kLinearRowsMaxM rows (linear_rows.hip); epi as linear_decode
+torch::Tensor linear_rows(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, int64_t epi) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16 &&
+                  x.dim() == 2 && w.dim() == 2 && x.stride(1) == 1 && w.stride(1) == 1 && x.device() == w.device(),
+              "linear_rows: x [M, K] and w [N, K] must be bf16 tensors on one ROCm device with unit column stride");
+  TORCH_CHECK(x.size(1) == w.size(1), "linear_rows: inner dimensions ", x.sizes(), " vs ", w.sizes());
+  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+  const int64_t ldx = x.stride(0), ldw = w.stride(0);
+  TORCH_CHECK(linear_rows_supported_op(M, N, K, ldx, ldw) && aligned16(x) && aligned16(w),
+              "linear_rows: unsupported shape M=", M, " N=", N, " K=", K, " (", sdml::kLinearDecodeMaxM, " < M <= ",
+              sdml::kLinearRowsMaxM, ", K % 64 == 0, N % 16 == 0, 16-byte aligned rows; linear_rows_supported)");
+  TORCH_CHECK(epi == sdml::EPI_STORE || epi == sdml::EPI_BIAS || epi == sdml::EPI_BIAS_GELU,
+              "linear_rows: unknown epilogue ", epi);
+  const void* bp = nullptr;
+  if (epi != sdml::EPI_STORE) {
+    TORCH_CHECK(bias.has_value() && bias->defined() && bias->is_cuda() && bias->scalar_type() == torch::kBFloat16 &&
+                    bias->is_contiguous() && bias->numel() == N && bias->device() == x.device(),
+                "linear_rows: bias must be a contiguous bf16 [N] device tensor");
+    bp = bias->data_ptr();
+  }
+  auto y = torch::empty({M, N}, x.options());
+  const size_t wsn = sdml::linear_rows_workspace_floats((int)M, (int)N, (int)K);
+  torch::Tensor ws;
+  if (wsn) ws = torch::empty({(int64_t)wsn}, x.options().dtype(torch::kFloat32));
+  sdml::linear_rows_bf16(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), wsn ? ws.data_ptr<float>() : nullptr, (int)M,
+                         (int)N, (int)K, (int)ldx, (int)ldw, (int)epi, cur_stream());
+  return y;
+}
+
 // tokens [B] int64 from bf16 logits [B, ld] (columns < vocab); temperature 0: greedy. pos: int32 [B] on the device.
 torch::Tensor sample_logits(torch::Tensor logits, int64_t vocab, double temperature, int64_t top_k, int64_t seed,
                             int64_t sample0, torch::Tensor pos, int64_t rows_per_sample) {
@@ -2732,6 +2766,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_decode_supported", &linear_decode_supported_op, "shapes linear_decode takes (M, N, K, ldx, ldw)");
   m.def("linear_decode_splits", [](int64_t N, int64_t K) { return sdml::linear_decode_splits((int)N, (int)K); },
         "grid-level K splits of linear_decode for (N, K)");
+  m.def("linear_rows", &linear_rows, "x @ w.T (+ bias) (GELU) for 64 < M <= 512 rows with linear_decode's bits (bf16)",
+        py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("epi") = 0);
+  m.def("linear_rows_supported", &linear_rows_supported_op, "shapes linear_rows takes (M, N, K, ldx, ldw)");
+  m.def("linear_rows_max_m", []() { return sdml::kLinearRowsMaxM; }, "linear_rows' row bound");
+  m.def("linear_rows_dispatch_m", []() { return sdml::kLinearRowsDispatchM; },
+        "rows up to which ops/decode.py prefers linear_rows to gemm_bf16");
   m.def("sample_logits", &sample_logits, "greedy / top-k Gumbel-max sampling of bf16 logits rows on the device",
         py::arg("logits"), py::arg("vocab"), py::arg("temperature"), py::arg("top_k"), py::arg("seed"),
         py::arg("sample0"), py::arg("pos"), py::arg("rows_per_sample") = 1);

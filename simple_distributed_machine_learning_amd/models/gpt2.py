@@ -407,7 +407,8 @@ class GPT2Stage(PipelineStage):
         ``head_rows`` = n > 1 (``generate(num_samples=n)``): the last stage returns [B n, ld], sample b's logits in
         rows b n .. b n + n - 1. The sample's last hidden row is repeated ahead of the lm_head, not the logits after
         it, so the head runs over B n rows through the entry point that the prefill of the n-fold repeated prompts
-        takes (``linear_decode`` up to 64 rows, the GEMM beyond) and the rows carry that call's bits."""
+        takes (``ops.decode.linear_decode``: linear_decode.hip up to 64 rows, linear_rows.hip with the same bits per
+        row up to ``LINEAR_ROWS_DISPATCH_M``, the GEMM beyond) and the rows carry that call's bits."""
         if self.stage_id == 0:
             x = embedding(x, self.wte.weight, self.wpe.weight)
         B, S, C = x.shape
@@ -576,8 +577,8 @@ class GPT2Stage(PipelineStage):
 
         The device-side length is NOT advanced: the caller's ``lookup_step`` does that by the accepted count, so the
         stages of one rank must share one ``cache.lens`` tensor. ``cache.n`` becomes the host's bound min(n + T,
-        smax). On ROCm bf16 B * T <= 64 is required (``linear_decode``'s rows): more rows would take another GEMM
-        with other bits, and are refused."""
+        smax). On ROCm bf16 B * T <= 64 is required (linear_decode.hip's rows) and more rows are refused; linear_rows.hip
+        keeps a row's bits beyond 64 rows, so the bound can be lifted in a later change."""
         self._bf16_cache_only("decode_block", cache)
         if x.dim() < 2 or not 1 <= x.shape[1] <= ATTENTION_APPEND_MAX_T:
             raise ValueError(f"decode_block: x must be [B, T(, C)] with T in 1..{ATTENTION_APPEND_MAX_T}, got "

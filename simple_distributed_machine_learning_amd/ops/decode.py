@@ -1,6 +1,6 @@
 """Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, attention_append.hip,
-attention_extend.hip, attention_fork.hip, attention_decode_fp8.hip, kv_quantize.hip, linear_decode.hip, sample.hip,
-lookup.hip, beam.hip) and their torch twins.
+attention_extend.hip, attention_fork.hip, attention_decode_fp8.hip, kv_quantize.hip, linear_decode.hip,
+linear_rows.hip, sample.hip, lookup.hip, beam.hip) and their torch twins.
 
 Dispatch: ROCm bf16 tensors (head width 64 for the attention) run the hand-written kernels, and a shape the kernels do
 not take is an error there, never a library call. CPU tensors, fp32 and other head widths run the twins below, which
@@ -18,6 +18,8 @@ from . import reference as _ref
 
 EPI_STORE, EPI_BIAS, EPI_BIAS_GELU = 0, 1, 5  # csrc/kernels/kernels.h GemmEpi
 LINEAR_DECODE_MAX_M = 64  # kLinearDecodeMaxM
+LINEAR_ROWS_MAX_M = 512  # kLinearRowsMaxM
+LINEAR_ROWS_DISPATCH_M = 512  # kLinearRowsDispatchM: measured against gemm_bf16 (README.md, "linear_rows")
 ATTENTION_APPEND_MAX_T = 8  # kAttnAppendMaxT
 ATTENTION_FORK_MAX_N = 64  # kAttnForkMaxN
 LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM = 7, 8  # kLookupMaxDrafts, kLookupMaxNgram
@@ -34,22 +36,35 @@ def linear_decode_supported(M: int, N: int, K: int, ldx: int = None, ldw: int = 
     return bool(kernels().linear_decode_supported(M, N, K, K if ldx is None else ldx, K if ldw is None else ldw))
 
 
+def linear_rows_supported(M: int, N: int, K: int, ldx: int = None, ldw: int = None) -> bool:
+    """Shapes linear_rows.hip takes: 64 < M <= 512, else ``linear_decode_supported``'s rules."""
+    return bool(kernels().linear_rows_supported(M, N, K, K if ldx is None else ldx, K if ldw is None else ldw))
+
+
 def linear_decode(x, w, b=None, gelu: bool = False, tickets=None):
     """y [M, N] = x [M, K] w[N, K]^T (+ b) (then tanh-GELU; needs b). ROCm bf16: linear_decode.hip for M <= 64 (W
-    streamed once over the whole chip), gemm_bf16.hip above that; anything else: torch.
+    streamed once over the whole chip); linear_rows.hip for 64 < M <= ``LINEAR_ROWS_DISPATCH_M`` where
+    ``linear_rows_supported`` holds (64-row panels of x in LDS; every row keeps the bits linear_decode.hip gives it,
+    so a row's result does not change when the batch crosses 64 rows); gemm_bf16.hip for more rows or another shape;
+    anything else: torch.
 
     ``tickets``: the one-launch form of linear_decode.hip. An int32 tensor on x's device with at least N / 16 entries,
     all zero on entry; the kernel leaves them zero. Where the shape is split over K, the last split to arrive at a
     column tile sums the tile instead of a second launch; the bits are those of the call without tickets. A wrong
-    dtype, device or size is a RuntimeError. The torch twins and the M > 64 path ignore it."""
+    dtype, device or size is a RuntimeError. The torch twins and the M > 64 paths ignore it."""
     if gelu and b is None:
         raise ValueError("linear_decode: the GELU epilogue comes with a bias")
     if _hip_bf16(x, w):
         epi = EPI_BIAS_GELU if gelu else (EPI_BIAS if b is not None else EPI_STORE)
-        if x.shape[0] <= LINEAR_DECODE_MAX_M:
+        M = x.shape[0]
+        if M <= LINEAR_DECODE_MAX_M:
             if tickets is None:
                 return kernels().linear_decode(x, w, b, epi)
             return kernels().linear_decode(x, w, b, epi, tickets)
+        if M <= LINEAR_ROWS_DISPATCH_M and x.dim() == 2 and w.dim() == 2 and x.stride(1) == 1 and w.stride(1) == 1 \
+                and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 \
+                and kernels().linear_rows_supported(M, w.shape[0], x.shape[1], x.stride(0), w.stride(0)):
+            return kernels().linear_rows(x, w, b, epi)
         return kernels().gemm_bf16(x, w, b, False, epi)[0]
     y = F.linear(x, w, b)
     return F.gelu(y, approximate="tanh") if gelu else y

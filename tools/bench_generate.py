@@ -44,6 +44,14 @@ hand kernels (the LayerNorm kernels are the same in both). The gate: hand >= lib
     strided copies it replaces at B = 16, S = 512;
   * the decode loop, eager and graph-replayed, at B = 16, ctx 512 and B = 64, ctx 1024;
   * the drift of the last-position logits after 128 greedy steps, fp8 teacher-forced on bf16's tokens.
+
+--rows measures only linear_rows, the projections at 65..512 rows, and writes --out_rows:
+  * per-kernel windows, linear_rows against gemm_bf16 alternated over --rounds, at the five shapes and M in 65, 96, 128,
+    192, 256, 384, 512; per M the sum over a decode step's projections (12 x four + the lm_head), and the largest M up
+    to which linear_rows' sum is not above gemm_bf16's in any round: LINEAR_ROWS_DISPATCH_M (ops/decode.py);
+  * the decode loop at B = 64, 65, 128, 256 and --ctx, eager and graph-replayed, with the wrapper's bound as committed
+    against the bound put at 64 rows (the loop as it ran before linear_rows). The gate: not slower in any round at
+    any B > 64.
 """
 import argparse
 import json
@@ -609,8 +617,113 @@ def main_fp8kv(a):
     return 0 if ok else 1
 
 
+# ---- linear_rows, the projections at 65..512 rows (--rows) ----------------------------------------------------------
+ROWS_M = (65, 96, 128, 192, 256, 384, 512)
+ROWS_LOOP_B = (64, 65, 128, 256)  # 64: the same code in both forms, reported only
+
+
+def bench_rows_kernels(rounds, reps, emit):
+    """linear_rows against gemm_bf16 (what the wrapper ran above 64 rows before linear_rows), windows as in
+    bench_kernels. Per M and round the five shapes are summed as a decode step of the 12-layer model uses them: 12 x
+    the four projections + the lm_head. Returns the largest M of ROWS_M up to which linear_rows' sum is not above
+    gemm_bf16's in any round (64: not even at 65)."""
+    K = _native.kernels()
+    total = {(k, M, r): 0.0 for k in ("linear_rows", "gemm_bf16") for M in ROWS_M for r in range(rounds)}
+    for name, (N, Kd) in SHAPES.items():
+        copies = max(2, min(reps, LLC_BYTES // (N * Kd * 2) + 1))
+        w = torch.randn(copies, N, Kd, device=DEV, dtype=BF) * 0.02
+        bias = None if name == "lm_head" else torch.randn(N, device=DEV, dtype=BF)
+        epi = 0 if name == "lm_head" else (5 if name == "c_fc" else 1)
+        for M in ROWS_M:
+            x = torch.randn(M, Kd, device=DEV, dtype=BF)
+            fns = {"linear_rows": lambda i: K.linear_rows(x, w[i % copies], bias, epi),
+                   "gemm_bf16": lambda i: K.gemm_bf16(x, w[i % copies], bias, False, epi)}
+            for fn in fns.values():
+                window(fn, copies)
+            for r in range(rounds):
+                for kname, fn in fns.items():  # alternated
+                    ms = window(fn, reps)
+                    total[(kname, M, r)] += ms * 1e3 * (1 if name == "lm_head" else 12)
+                    emit({"kernel": kname, "shape": name, "M": M, "N": N, "K": Kd, "round": r,
+                          "us": round(ms * 1e3, 2), "copies": copies})
+        del w
+    bound = 64
+    for i, M in enumerate(ROWS_M):
+        rows = [round(total[("linear_rows", M, r)], 1) for r in range(rounds)]
+        gemm = [round(total[("gemm_bf16", M, r)], 1) for r in range(rounds)]
+        wins = all(a <= b for a, b in zip(rows, gemm))
+        if wins and bound == (ROWS_M[i - 1] if i else 64):
+            bound = M
+        emit({"summary": "projections of one decode step (12 x four + lm_head)", "M": M, "linear_rows_us": rows,
+              "gemm_bf16_us": gemm, "linear_rows_not_slower_every_round": bool(wins)})
+    emit({"summary": "LINEAR_ROWS_DISPATCH_M", "measured": bound})
+    return bound
+
+
+@torch.no_grad()
+def bench_rows_loop(engine, ctx, steps, rounds, emit):
+    """The decode loop with linear_rows against the loop as it ran before it (the wrapper's bound put at 64 rows, so
+    that more rows go to gemm_bf16), eager and graph-replayed, alternated. The gate: with linear_rows not slower in any
+    round at any B > 64."""
+    from simple_distributed_machine_learning_amd.ops import decode as dec
+    bound = dec.LINEAR_ROWS_DISPATCH_M
+    forms = [(k, g) for g in (False, True) for k in ("linear_rows", "gemm_bf16")]
+    ok = True
+    try:
+        for B in ROWS_LOOP_B:
+            ses = {}
+            for k, g in forms:
+                dec.LINEAR_ROWS_DISPATCH_M = bound if k == "linear_rows" else 64
+                if g:
+                    ses[k] = graph_session(engine, B, ctx, steps, None)
+                    run_graph_loop(*ses[k], 8)
+                else:
+                    run_loop(engine, B, ctx, 8, True)
+            tps = {f: [] for f in forms}
+            for r in range(rounds):
+                for k, g in forms:  # alternated
+                    dec.LINEAR_ROWS_DISPATCH_M = bound if k == "linear_rows" else 64
+                    s = run_graph_loop(*ses[k], steps) if g else run_loop(engine, B, ctx, steps, True)
+                    tps[(k, g)].append(round(B * steps / s, 1))
+                    emit({"loop": f"{k} {'graph' if g else 'eager'}", "B": B, "ctx": ctx, "steps": steps, "round": r,
+                          "ms_per_step": round(s / steps * 1e3, 4), "tokens_per_s": tps[(k, g)][-1]})
+            rec = {"summary": "decode loop, rows above 64", "B": B, "ctx": ctx,
+                   **{f"{k}_{'graph' if g else 'eager'}_tokens_per_s": v for (k, g), v in tps.items()}}
+            if B > 64:
+                gate = all(a >= b for g in (False, True) for a, b in zip(tps[("linear_rows", g)], tps[("gemm_bf16", g)]))
+                rec["gate_linear_rows_not_slower_every_round"] = bool(gate)
+                ok = ok and gate
+            emit(rec)
+            del ses
+            torch.cuda.empty_cache()
+    finally:
+        dec.LINEAR_ROWS_DISPATCH_M = bound
+    return ok
+
+
+def main_rows(a):
+    os.makedirs(os.path.dirname(a.out_rows) or ".", exist_ok=True)
+    with open(a.out_rows, "w") as f:
+        def emit(rec):
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+
+        if not a.no_kernels:
+            bench_rows_kernels(a.rounds, a.reps, emit)
+        mesh = init_mesh(pp=1, schedule_kind="1f1b", rank=0, world_size=1, device=DEV)
+        engine = PipelineEngine(get_model_spec("gpt2", 2), mesh, schedule_kind="1f1b", num_microbatches=1)
+        engine.eval()
+        ok = bench_rows_loop(engine, a.ctx, a.steps, a.rounds, emit)
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", action="store_true",
+                    help="only linear_rows: its windows against gemm_bf16 at 65..512 rows and the decode loops at B > 64")
+    ap.add_argument("--out_rows", default="profiles/linear_rows.jsonl")
     ap.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: only the fp8 KV cache's windows, loops and drift, written to --out_fp8kv")
     ap.add_argument("--out_fp8kv", default="profiles/generate_fp8kv.jsonl")
@@ -631,6 +744,8 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py measures on the GPU; none is visible")
+    if a.rows:
+        return main_rows(a)
     if a.kv_dtype == "fp8":
         return main_fp8kv(a)
     if a.graph:
