@@ -121,13 +121,14 @@ KEY_MARKER = b"SDML_BUILD_KEY="
 # Flags of single kernel files. beam.hip is compiled with the packed fp32 instructions (v_pk_add_f32, v_pk_mul_f32,
 # v_pk_fma_f32) switched off in the code generator. Today its device code is the same with and without the flag (no
 # packed instruction either way, 128 VGPRs, 8 spilled): the flag is a guard, so that no later edit or compiler makes
-# the reductions' adds packed ones; the older files keep the flags they were tuned and measured with. The fp8 KV-cache
-# kernels (fma chains and scales over register arrays, which the packer would pair) are compiled the same way, and so
+# the reductions' adds packed ones; the older files keep the flags they were tuned and measured with. The fp8 and fp4
+# KV-cache kernels (fma chains and scales over register arrays, which the packer would pair) are compiled the same way, and so
 # is sample_penalty.hip (the penalty's multiply and the logprob's sums must stay single fp32 operations); it is a file
 # of its own beside sample.hip for that reason: the flag changes embed_at_kernel's code there.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 KERNEL_FILE_FLAGS = {"beam.hip": _NO_PACKED_FP32, "kv_quantize.hip": _NO_PACKED_FP32,
-                     "attention_decode_fp8.hip": _NO_PACKED_FP32, "sample_penalty.hip": _NO_PACKED_FP32}
+                     "attention_decode_fp8.hip": _NO_PACKED_FP32, "sample_penalty.hip": _NO_PACKED_FP32,
+                     "kv_quantize_fp4.hip": _NO_PACKED_FP32, "attention_decode_fp4.hip": _NO_PACKED_FP32}
 
 
 def _plan(what: str):

@@ -541,6 +541,25 @@ struct KvFp8Args {
 };
 void kv_quantize_rows_fp8(const KvFp8Args& a, hipStream_t stream);
 void attention_decode_fp8(const KvFp8Args& a, hipStream_t stream);
+// ---- fp4 KV cache (kv_fp4.h, kv_quantize_fp4.hip, attention_decode_fp4.hip; ops/decode.py kv_quantize_fp4) ----------
+// A cache row (sample, key, head) is two MX blocks of 32 channels: 16 bytes of e2m1 nibbles (channel 2 i the low
+// nibble of byte i) and one int8 exponent e per block, value = e2m1(nibble) * 2^e, e the smallest integer with
+// amax * 2^-e <= 6, clamped to [-120, 120], 0 for an all-zero block. k4 / v4 [B][Smax][H][32] uint8 and ke / ve
+// [B][H][Smax][2] int8, all contiguous: 34 bytes per row. The two entry points mirror the fp8 pair's semantics.
+// run: consecutive chunks of one (sample, head) that a wave of attention_decode_fp4 owns, 0 = chosen from the grid's
+// size; every chunk writes its own slot, so the result's bits do not depend on it.
+struct KvFp4Args {
+  const void* qkv = nullptr;
+  void *k4 = nullptr, *v4 = nullptr, *out = nullptr;
+  signed char *ke = nullptr, *ve = nullptr;
+  const int* lens = nullptr;
+  float *ws_ml = nullptr, *ws_o = nullptr;
+  int B = 0, H = 0, S = 0, Smax = 0, max_chunks = 0, run = 0;
+  long ldq = 0, sqb = 0;
+  float scale = 1.f;
+};
+void kv_quantize_rows_fp4(const KvFp4Args& a, hipStream_t stream);
+void attention_decode_fp4(const KvFp4Args& a, hipStream_t stream);
 // T = 1 .. kAttnAppendMaxT new tokens per sample against the cache (attention_append.hip). qkv [B][T] rows of ldq
 // elements, nq [B] int32 on the device: live queries per sample. Query t is live iff t < nq[b] and lens[b] + t <
 // n_keys (the host's bound, 1 <= n_keys <= Smax; max_chunks = attention_decode_chunks(n_keys)). A live query writes

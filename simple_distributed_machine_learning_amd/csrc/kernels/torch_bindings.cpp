@@ -2233,6 +2233,81 @@ torch::Tensor attention_decode_fp8(torch::Tensor qkv, torch::Tensor k8, torch::T
   return out;
 }
 
+// an fp4 cache (kernels.h KvFp4Args): k4 / v4 [B, Smax, H, 32] uint8 and ke / ve [B, H, Smax, 2] int8, contiguous, on
+// `like`'s device; fills the args' pointers and B, H, Smax
+static void check_kv_fp4(const char* who, const torch::Tensor& k4, const torch::Tensor& ke, const torch::Tensor& v4,
+                         const torch::Tensor& ve, const torch::Tensor& like, sdml::KvFp4Args& a) {
+  for (const torch::Tensor* t : {&k4, &v4})
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device() && t->scalar_type() == torch::kUInt8 && t->dim() == 4 &&
+                    t->is_contiguous() && aligned16(*t),
+                who, ": k4 / v4 must be contiguous uint8 [B, Smax, H, 32] tensors on qkv's device, got ",
+                t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(k4.size(3) == 32, who, ": head width 64 (32 bytes of nibbles), got ", k4.size(3), " bytes");
+  TORCH_CHECK(k4.sizes() == v4.sizes(), who, ": k4 ", k4.sizes(), " and v4 ", v4.sizes(), " differ");
+  const int64_t B = k4.size(0), Smax = k4.size(1), H = k4.size(2);
+  for (const torch::Tensor* t : {&ke, &ve})
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device() && t->scalar_type() == torch::kInt8 && t->dim() == 4 &&
+                    t->is_contiguous() && t->size(0) == B && t->size(1) == H && t->size(2) == Smax && t->size(3) == 2,
+                who, ": ke / ve must be contiguous int8 [B, H, Smax, 2] = [", B, ", ", H, ", ", Smax,
+                ", 2] tensors on qkv's device, got ", t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(B >= 1 && 2 * B <= 65535 && H >= 1 && H <= 65535 && Smax >= 1 && Smax < (1 << 29), who,
+              ": batch / heads out of the grid's range");
+  a.k4 = k4.data_ptr(), a.v4 = v4.data_ptr();
+  a.ke = ke.data_ptr<int8_t>(), a.ve = ve.data_ptr<int8_t>();
+  a.B = (int)B, a.H = (int)H, a.Smax = (int)Smax;
+}
+
+// qkv [B, S', 3C] bf16 (a layer's fused projection of the prompt): quantises the k and v of positions 0..S-1 into the
+// fp4 cache, rows 0..S-1, in one launch (kv_quantize_fp4.hip)
+void kv_quantize_rows_fp4(torch::Tensor qkv, torch::Tensor k4, torch::Tensor ke, torch::Tensor v4, torch::Tensor ve,
+                          int64_t S) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 3 && qkv.stride(2) == 1,
+              "kv_quantize_rows_fp4: qkv must be a [B, S, 3C] bf16 device tensor with unit column stride");
+  sdml::KvFp4Args a;
+  check_kv_fp4("kv_quantize_rows_fp4", k4, ke, v4, ve, qkv, a);
+  TORCH_CHECK(qkv.size(0) == a.B && qkv.size(2) == 3 * 64 * (int64_t)a.H, "kv_quantize_rows_fp4: qkv ", qkv.sizes(),
+              " does not match a ", k4.sizes(), " cache");
+  TORCH_CHECK(S >= 0 && S <= qkv.size(1) && S <= a.Smax, "kv_quantize_rows_fp4: S = ", S,
+              " positions, but qkv has ", qkv.size(1), " and the cache ", a.Smax, " rows");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && qkv.stride(0) >= 0 && qkv.stride(1) >= 0 &&
+                  aligned16(qkv),
+              "kv_quantize_rows_fp4: 16-byte aligned rows required");
+  a.qkv = qkv.data_ptr();
+  a.S = (int)S, a.sqb = qkv.stride(0), a.ldq = qkv.stride(1);
+  sdml::kv_quantize_rows_fp4(a, cur_stream());
+}
+
+// attention_decode on an fp4 cache (attention_decode_fp4.hip): qkv [B, 3C] bf16, lens int32 [B], n_keys the host's
+// bound lens[b] + 1 <= n_keys <= Smax. Quantises the new k, v into cache row lens[b]; returns [B, C] bf16. run: the
+// chunks a wave owns, 1..4, 0 = chosen from the grid's size; the result's bits do not depend on it.
+torch::Tensor attention_decode_fp4(torch::Tensor qkv, torch::Tensor k4, torch::Tensor ke, torch::Tensor v4,
+                                   torch::Tensor ve, torch::Tensor lens, double scale, int64_t n_keys, int64_t run) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1,
+              "attention_decode_fp4: qkv must be a [B, 3C] bf16 device tensor with unit column stride");
+  sdml::KvFp4Args a;
+  check_kv_fp4("attention_decode_fp4", k4, ke, v4, ve, qkv, a);
+  const int64_t B = a.B, H = a.H, C = H * 64;
+  TORCH_CHECK(qkv.size(0) == B && qkv.size(1) == 3 * C, "attention_decode_fp4: qkv ", qkv.sizes(),
+              " does not match a ", k4.sizes(), " cache");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && qkv.stride(0) >= 0 && aligned16(qkv),
+              "attention_decode_fp4: 16-byte aligned rows required");
+  a.lens = device_i32("attention_decode_fp4", "lens", "B", lens, B, qkv);
+  TORCH_CHECK(n_keys >= 1 && n_keys <= a.Smax, "attention_decode_fp4: the cache is full: ", n_keys,
+              " keys with the new one, ", a.Smax, " rows (lens[b] + 1 <= n_keys <= Smax)");
+  TORCH_CHECK(run >= 0 && run <= 4, "attention_decode_fp4: run must be 0 (default) or 1..4, got ", run);
+  a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
+  a.run = (int)run;
+  auto out = torch::empty({B, C}, qkv.options());
+  auto ws = torch::empty({B * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
+  a.qkv = qkv.data_ptr(), a.out = out.data_ptr();
+  a.ws_o = ws.data_ptr<float>();
+  a.ws_ml = a.ws_o + B * H * a.max_chunks * 64;
+  a.ldq = qkv.stride(0);
+  a.scale = (float)scale;
+  sdml::attention_decode_fp4(a, cur_stream());
+  return out;
+}
+
 // qkv [B, T, 3C] (T = 1..8 new tokens per sample), the caches as attention_decode takes them, lens / nq int32 [B] on
 // the device: keys already cached and live queries per sample. Query t is live iff t < nq[b] and lens[b] + t <
 // n_keys. Writes the live queries' k, v at cache rows lens[b] + t; returns [B, T, C], zeros for dead queries.
@@ -2736,6 +2811,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "quantises and writes k, v at row lens[b], returns [B, C]",
         py::arg("qkv"), py::arg("k8"), py::arg("ke"), py::arg("v8"), py::arg("ve"), py::arg("lens"), py::arg("scale"),
         py::arg("n_keys"));
+  m.def("attention_decode_fp4", &attention_decode_fp4,
+        "attention_decode on an fp4 KV cache (e2m1 nibbles [B, Smax, H, 32] + int8 block exponents [B, H, Smax, 2]): "
+        "quantises and writes k, v at row lens[b], returns [B, C]",
+        py::arg("qkv"), py::arg("k4"), py::arg("ke"), py::arg("v4"), py::arg("ve"), py::arg("lens"), py::arg("scale"),
+        py::arg("n_keys"), py::arg("run") = 0);
+  m.def("kv_quantize_rows_fp4", &kv_quantize_rows_fp4,
+        "the k and v of positions 0..S-1 of qkv [B, S', 3C] bf16 into an fp4 KV cache, one launch",
+        py::arg("qkv"), py::arg("k4"), py::arg("ke"), py::arg("v4"), py::arg("ve"), py::arg("S"));
   m.def("kv_quantize_rows", &kv_quantize_rows,
         "the k and v of positions 0..S-1 of qkv [B, S', 3C] bf16 into an fp8 KV cache, one launch",
         py::arg("qkv"), py::arg("k8"), py::arg("ke"), py::arg("v8"), py::arg("ve"), py::arg("S"));

@@ -18,7 +18,8 @@ then counts verify steps. ``--num_samples N`` prints N continuations of every pr
 first (one rank; the prompt is prefilled and its keys are stored once). ``--metrics`` gets one ``generate`` event: the
 tokens really generated over all rows, seconds, tokens/s, graph, lookup, lookup_ngram, steps, tokens per step and
 num_samples. ``--kv_dtype fp8`` keeps the KV cache as e4m3 bytes with one exponent per row (half the bytes a decode
-step streams; the plain loop and ``--graph`` only); the event carries ``kv_dtype``. ``--repetition_penalty THETA``
+step streams; the plain loop and ``--graph`` only), ``--kv_dtype fp4`` as e2m1 nibbles with one exponent per 32
+channels (a quarter of the bytes, a much coarser rounding); the event carries ``kv_dtype``. ``--repetition_penalty THETA``
 and ``--no_repeat_ngram_size N`` make the sampler read the row's own history (parallel/generate.py; not with ``--lookup``
 or ``--num_beams``); ``--logprobs`` prints `` logprob=<sum>`` after a row's tokens, the model's log-probability of what
 the row generated. The event carries the two knobs.
@@ -99,8 +100,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --num_beams: rank a prompt's hypotheses by score / length ** this (0: the raw score)")
     s.add_argument("--return_beams", action="store_true",
                    help="with --num_beams: print all K hypotheses of every prompt, best first")
-    s.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"],
-                   help="the KV cache's storage: fp8 is e4m3 bytes with one int8 exponent per row, 66 bytes for 128 "
+    s.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8", "fp4"],
+                   help="the KV cache's storage: fp8 is e4m3 bytes with one int8 exponent per row, 66 bytes for 128; fp4 "
+                        "is e2m1 nibbles with one int8 exponent per 32 channels, 34 bytes "
                         "(not with --lookup, --num_samples, --num_beams or --prefill_chunk)")
     s.add_argument("--repetition_penalty", type=float, default=1.0, metavar="THETA",
                    help="scale the logits of the tokens a row already holds: times THETA where negative, divided by "

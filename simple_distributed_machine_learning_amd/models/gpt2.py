@@ -30,8 +30,9 @@ import torch.nn.functional as F
 
 from .base import ModelSpec, PipelineStage
 from ..ops.decode import (ATTENTION_APPEND_MAX_T, ATTENTION_FORK_MAX_N, BEAM_MAX_K, KV_DTYPES, LINEAR_DECODE_MAX_M,
-                          attention_append, attention_decode, attention_decode_fp8, attention_extend, attention_fork,
-                          beam_gather_kv, embedding_at, kv_quantize_rows, linear_decode)
+                          attention_append, attention_decode, attention_decode_fp4, attention_decode_fp8, attention_extend,
+                          attention_fork, beam_gather_kv, embedding_at, kv_fp4_blocks, kv_quantize_rows, kv_quantize_rows_fp4,
+                          linear_decode)
 from ..ops.linear import Linear, _w_padded, linear, lm_head, mlp_gelu
 from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
                              dropout_threshold)
@@ -276,7 +277,9 @@ class GPT2Stage(PipelineStage):
         buffer with a slice of its own per call site (four projections and the attention of every local layer; the
         lm_head is not split over K and needs none). ``kv_dtype`` "fp8": K and V are e4m3 bytes, uint8
         [B, Smax, H, D], with one int8 exponent per row in ``ke`` / ``ve`` [B, H, Smax] (ops/decode.py kv_quantize):
-        66 bytes per row where the parameters' dtype takes 2 D. ``prefill`` and ``decode_step`` serve such a cache."""
+        66 bytes per row where the parameters' dtype takes 2 D. "fp4": e2m1 nibbles, uint8 [B, Smax, H, D / 2], with
+        one int8 exponent per block of 32 channels in ``ke`` / ``ve`` [B, H, Smax, D / 32] (kv_quantize_fp4): 34 bytes.
+        ``prefill`` and ``decode_step`` serve such a cache."""
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"new_cache: kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
         if Smax > self.cfg.block_size:
@@ -291,6 +294,11 @@ class GPT2Stage(PipelineStage):
         if fused:
             tickets = torch.zeros(n * sum(self._ticket_sizes(B)), dtype=torch.int32, device=p.device)
         lens = torch.zeros(B, dtype=torch.int32, device=p.device)
+        if kv_dtype == "fp4":
+            mk4 = lambda: torch.empty((B, Smax, H, D // 2), dtype=torch.uint8, device=p.device)  # noqa: E731
+            mke = lambda: torch.empty((B, H, Smax, kv_fp4_blocks(D)), dtype=torch.int8, device=p.device)  # noqa: E731
+            return KVCache([mk4() for _ in range(n)], [mk4() for _ in range(n)], lens, 0, Smax, tickets, "fp4",
+                           [mke() for _ in range(n)], [mke() for _ in range(n)])
         if kv_dtype == "fp8":
             mk8 = lambda: torch.empty((B, Smax, H, D), dtype=torch.uint8, device=p.device)  # noqa: E731
             mke = lambda: torch.empty((B, H, Smax), dtype=torch.int8, device=p.device)  # noqa: E731
@@ -306,6 +314,11 @@ class GPT2Stage(PipelineStage):
     @staticmethod
     def _decode_attention(cache: "KVCache", H: int, n_keys: int, tickets=None):
         """decode_step's attention call on block i's fused projection, by the cache's kv_dtype."""
+        if cache.kv_dtype == "fp4":
+            if tickets is not None and any(t["attn"] is not None for t in tickets):
+                raise ValueError("decode_step: the attention over an fp4 cache has no one-launch (tickets) form")
+            return lambda i, qkv: attention_decode_fp4(qkv, cache.k[i], cache.ke[i], cache.v[i], cache.ve[i],
+                                                       cache.lens, H, n_keys)
         if cache.kv_dtype == "fp8":
             if tickets is not None and any(t["attn"] is not None for t in tickets):
                 raise ValueError("decode_step: the attention over an fp8 cache has no one-launch (tickets) form")
@@ -419,7 +432,9 @@ class GPT2Stage(PipelineStage):
 
         def attn(i, blk, y):
             qkv = blk.attn.c_attn(y)
-            if cache.kv_dtype == "fp8":  # (the flash kernel below still reads the prompt's unquantised k and v)
+            if cache.kv_dtype == "fp4":  # (the flash kernel below still reads the prompt's unquantised k and v)
+                kv_quantize_rows_fp4(qkv, cache.k[i], cache.ke[i], cache.v[i], cache.ve[i], S)
+            elif cache.kv_dtype == "fp8":
                 kv_quantize_rows(qkv, cache.k[i], cache.ke[i], cache.v[i], cache.ve[i], S)
             else:
                 cache.k[i][:, :S].copy_(qkv[..., C:2 * C].view(B, S, H, C // H))
@@ -636,7 +651,9 @@ class KVCache:
     cached per sample, what the kernels read); ``n`` the host's bound on them (the count itself after an equal-length
     prefill, the longest row's after a ragged one; all samples advance together), so the bounds are checked without
     reading the device. ``kv_dtype`` "fp8": ``k`` / ``v`` hold e4m3 bytes (uint8) and ``ke`` / ``ve`` the rows' int8
-    exponents [B, H, Smax] per local layer (ops/decode.py kv_quantize)."""
+    exponents [B, H, Smax] per local layer (ops/decode.py kv_quantize). "fp4": ``k`` / ``v`` hold e2m1 nibbles
+    [B, Smax, H, D / 2] and ``ke`` / ``ve`` the int8 exponents of the 32-channel blocks [B, H, Smax, D / 32]
+    (kv_quantize_fp4)."""
     k: list
     v: list
     lens: torch.Tensor

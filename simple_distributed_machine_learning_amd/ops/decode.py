@@ -1,5 +1,6 @@
 """Generation-time ops: the wrappers of the decode kernels (csrc/kernels/attention_decode.hip, attention_append.hip,
-attention_extend.hip, attention_fork.hip, attention_decode_fp8.hip, kv_quantize.hip, linear_decode.hip,
+attention_extend.hip, attention_fork.hip, attention_decode_fp8.hip, kv_quantize.hip, attention_decode_fp4.hip,
+kv_quantize_fp4.hip, linear_decode.hip,
 linear_rows.hip, sample.hip, lookup.hip, beam.hip) and their torch twins.
 
 Dispatch: ROCm bf16 tensors (head width 64 for the attention) run the hand-written kernels, and a shape the kernels do
@@ -118,7 +119,7 @@ def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int, tick
 
 
 # ---- fp8 KV cache (csrc/kernels/kv_fp8.h, kv_quantize.hip, attention_decode_fp8.hip; docs/NUMERICS.md) ---------------
-KV_DTYPES = ("bf16", "fp8")
+KV_DTYPES = ("bf16", "fp8", "fp4")
 KV_EXP_MIN, KV_EXP_MAX = -120, 120  # kv_fp8.h kExpMin, kExpMax
 
 
@@ -215,6 +216,127 @@ def attention_decode_fp8(qkv, k8, ke, v8, ve, lens, n_head: int, n_keys: int):
     if _hip_bf16(qkv) and k8.is_cuda and k8.shape[-1] == 64:
         return kernels().attention_decode_fp8(qkv, k8, ke, v8, ve, lens, 1.0 / math.sqrt(64), int(n_keys))
     return attention_decode_fp8_ref(qkv, k8, ke, v8, ve, lens, n_head, n_keys)
+
+
+# ---- fp4 KV cache (csrc/kernels/kv_fp4.h, kv_quantize_fp4.hip, attention_decode_fp4.hip; docs/NUMERICS.md) -----------
+KV_FP4_BLOCK = 32  # channels per MX block: 16 bytes of nibbles and one exponent
+
+
+def kv_fp4_blocks(D: int) -> int:
+    """Blocks per row of D channels: D / 32, or one block for an even D that is no multiple of 32 (the twin only)."""
+    return D // KV_FP4_BLOCK if D % KV_FP4_BLOCK == 0 else 1
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# (threshold, inclusive): a magnitude's code is the count of thresholds it passes; a tie goes to the even code
+_E2M1_TIES = ((0.25, False), (0.75, True), (1.25, False), (1.75, True), (2.5, False), (3.5, True), (5.0, False))
+
+
+def kv_quantize_fp4(x):
+    """The fp4 KV-cache format (OCP microscaling e2m1), which the kernels reproduce bit for bit. x [..., D], D a
+    multiple of 32: rows of D / 32 blocks (``kv_fp4_blocks``: a narrower row is one block, for small models on the
+    twin). Returns (bytes uint8 [..., D / 2], exps int8 [..., D / 32]). A block is 32 channels: 16 bytes, channel 2 i the low nibble of byte i and channel 2 i + 1 the high one, and one exponent e; the
+    value is e2m1(nibble) * 2^e. A nibble is sign, two exponent bits, one mantissa bit: magnitudes {0, 0.5, 1, 1.5, 2,
+    3, 4, 6}. e is the smallest integer with amax * 2^-e <= 6 (amax = f 2^x, f in [1, 2): x - 2 if f <= 1.5, else
+    x - 1), clamped to [-120, 120], and 0 for an all-zero block: the scaled block peaks in (3, 6] and never saturates.
+    x * 2^-e is exact, so the round-to-nearest-even onto the e2m1 grid is the only rounding (ties to the code with
+    mantissa bit 0: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); the sign is kept, -0
+    included. Finite inputs only: e2m1 has no NaN or Inf, and what a non-finite input becomes is not specified."""
+    xf = x.float().unflatten(-1, (kv_fp4_blocks(x.shape[-1]), -1))
+    amax = xf.abs().amax(-1)
+    f, ex = torch.frexp(amax)  # amax = f 2^ex with f in [0.5, 1)
+    e = ex - 1 - torch.where(f <= 0.75, 2, 1)
+    e = torch.where(amax == 0, torch.zeros_like(e), e.clamp(KV_EXP_MIN, KV_EXP_MAX))
+    y = xf * _pow2(-e)[..., None]
+    a = y.abs()
+    code = torch.zeros_like(a, dtype=torch.uint8)
+    for t, inclusive in _E2M1_TIES:
+        code += (a >= t) if inclusive else (a > t)
+    code |= torch.signbit(y).to(torch.uint8) << 3
+    q = code[..., 0::2] | (code[..., 1::2] << 4)
+    return q.flatten(-2), e.to(torch.int8)
+
+
+def kv_dequantize_fp4(q, e):
+    """fp32 [..., D] = e2m1(nibbles of q) * 2^e for bytes uint8 [..., D / 2] and exponents int8 [..., D / 32]: exact."""
+    nib = torch.stack((q & 0xF, q >> 4), -1).flatten(-2).to(torch.int64)
+    mag = torch.tensor(_E2M1, dtype=torch.float32, device=q.device)[nib & 7]
+    val = torch.where((nib & 8) != 0, -mag, mag).unflatten(-1, (e.shape[-1], -1))
+    return (val * _pow2(e)[..., None]).flatten(-2)
+
+
+def _check_kv_fp4(who: str, qkv, k4, ke, v4, ve):
+    B, Smax, H = k4.shape[:3] if k4.dim() == 4 else (0, 0, 0)
+    nb = kv_fp4_blocks(2 * k4.shape[3]) if k4.dim() == 4 else 0
+    if k4.dim() != 4 or k4.shape != v4.shape or ke.shape != (B, H, Smax, nb) or ve.shape != ke.shape or \
+            k4.dtype != torch.uint8 or v4.dtype != torch.uint8 or \
+            ke.dtype != torch.int8 or ve.dtype != torch.int8:
+        raise ValueError(f"{who}: an fp4 cache is k4 / v4 uint8 [B, Smax, H, D / 2] with ke / ve int8 "
+                         f"[B, H, Smax, D / 32], got {k4.dtype} {tuple(k4.shape)}, {ke.dtype} {tuple(ke.shape)}, "
+                         f"{v4.dtype} {tuple(v4.shape)}, {ve.dtype} {tuple(ve.shape)}")
+    if qkv.shape[0] != B or qkv.shape[-1] != 3 * H * 2 * k4.shape[3]:
+        raise ValueError(f"{who}: qkv {tuple(qkv.shape)} does not match a {tuple(k4.shape)} cache")
+
+
+def kv_quantize_rows_fp4_ref(qkv, k4, ke, v4, ve, S: int):
+    """The twin: ``kv_quantize_fp4`` of the k and v of positions 0..S-1 of qkv [B, S', 3C] into cache rows 0..S-1."""
+    B, _, H, D2 = k4.shape
+    C = H * 2 * D2
+    for o, (q4, ex) in enumerate(((k4, ke), (v4, ve)), 1):
+        q, e = kv_quantize_fp4(qkv[:, :S, o * C:(o + 1) * C].reshape(B, S, H, 2 * D2))
+        q4[:, :S] = q
+        ex[:, :, :S] = e.transpose(1, 2)
+
+
+def kv_quantize_rows_fp4(qkv, k4, ke, v4, ve, S: int):
+    """Prefill's write of an fp4 cache: the k and v of positions 0..S-1 of a layer's fused projection qkv [B, S', 3C]
+    become the nibbles k4 / v4 [B, Smax, H, D / 2] uint8 and block exponents ke / ve [B, H, Smax, D / 32] int8 of rows
+    0..S-1 (``kv_quantize_fp4`` is the format). ROCm bf16 with D = 64: kv_quantize_fp4.hip, one launch for both
+    operands."""
+    _check_kv_fp4("kv_quantize_rows_fp4", qkv, k4, ke, v4, ve)
+    if qkv.dim() != 3 or not 0 <= S <= min(qkv.shape[1], k4.shape[1]):
+        raise ValueError(f"kv_quantize_rows_fp4: S = {S} positions of qkv {tuple(qkv.shape)} into a cache of "
+                         f"{k4.shape[1]} rows")
+    if _hip_bf16(qkv) and k4.is_cuda and k4.shape[-1] == 32:
+        return kernels().kv_quantize_rows_fp4(qkv, k4, ke, v4, ve, int(S))
+    return kv_quantize_rows_fp4_ref(qkv, k4, ke, v4, ve, int(S))
+
+
+def attention_decode_fp4_ref(qkv, k4, ke, v4, ve, lens, n_head: int, n_keys: int):
+    """The twin: quantise the new k, v (``kv_quantize_fp4``) and write nibbles and exponents at cache row lens[b]; then
+    ``attention_decode_ref``'s lines on the dequantised cache, the new row included as dequantised. Rows at or past
+    lens[b] other than the new one are selected away there."""
+    B, C3 = qkv.shape
+    C = C3 // 3
+    D = C // n_head
+    idx = lens.to(torch.int64)
+    rows = torch.arange(B, device=qkv.device)
+    new = [qkv[:, :C].float()]
+    for o, (q4, ex) in enumerate(((k4, ke), (v4, ve)), 1):
+        q, e = kv_quantize_fp4(qkv[:, o * C:(o + 1) * C].view(B, n_head, D))
+        q4[rows, idx] = q
+        ex[rows, :, idx] = e
+        new.append(kv_dequantize_fp4(q, e).reshape(B, C))
+    kd = kv_dequantize_fp4(k4[:, :n_keys], ke[:, :, :n_keys].transpose(1, 2))
+    vd = kv_dequantize_fp4(v4[:, :n_keys], ve[:, :, :n_keys].transpose(1, 2))
+    return attention_decode_ref(torch.cat(new, 1), kd, vd, lens, n_head, n_keys).to(qkv.dtype)
+
+
+def attention_decode_fp4(qkv, k4, ke, v4, ve, lens, n_head: int, n_keys: int, run: int = 0):
+    """``attention_decode`` on an fp4 KV cache: k4 / v4 [B, Smax, H, D / 2] uint8 with ke / ve [B, H, Smax, D / 32]
+    int8 (``kv_quantize_fp4`` is the format; all four contiguous). The new token's k and v are quantised, written to
+    cache row lens[b], nibbles and exponents, and scored as the dequantised row, so the result is the attention over
+    the cache as later steps read it. Returns [B, C]; ``lens`` is not changed; ``n_keys`` as ``attention_decode`` takes
+    it. ROCm bf16 with D = 64: attention_decode_fp4.hip and attention_decode.hip's combine, two launches, no
+    one-launch form. ``run``: the consecutive 64-key chunks one wave of the kernel owns, 1..4, 0: chosen from the
+    grid's size; the result's bits do not depend on it (the twin ignores it)."""
+    _check_kv_fp4("attention_decode_fp4", qkv, k4, ke, v4, ve)
+    Smax = k4.shape[1]
+    if not 1 <= n_keys <= Smax:
+        raise ValueError(f"attention_decode_fp4: {n_keys} keys with the new one, but the cache has {Smax} rows")
+    if not 0 <= run <= 4:
+        raise ValueError(f"attention_decode_fp4: run must be 0 or 1..4, got {run}")
+    if _hip_bf16(qkv) and k4.is_cuda and k4.shape[-1] == 32:
+        return kernels().attention_decode_fp4(qkv, k4, ke, v4, ve, lens, 1.0 / math.sqrt(64), int(n_keys), int(run))
+    return attention_decode_fp4_ref(qkv, k4, ke, v4, ve, lens, n_head, n_keys)
 
 
 def _check_lens_nq(who: str, B: int, lens, nq):

@@ -71,6 +71,11 @@ depend on the batch, and ``graph=True`` replays them bit for bit. It serves the 
 eos, top-k, top-p) and ``graph=True``; it is refused with ``lookup > 0``, ``num_samples > 1``, ``num_beams > 1``,
 ``prefill_chunk > 0`` and by ``GenerationSession``. ``"bf16"`` (the default) runs the lines it always ran.
 
+``kv_dtype="fp4"`` is the same path on OCP microscaling e2m1 (ops/decode.py ``kv_quantize_fp4``: 16 bytes of nibbles
+and one int8 exponent per block of 32 channels, 34 bytes per row): ``kv_quantize_rows_fp4`` in the prefill,
+``attention_decode_fp4`` in every step. It serves and refuses what ``"fp8"`` does; its rounding is much coarser
+(docs/NUMERICS.md "fp4 KV cache" has the bound and the measured drift).
+
 ``repetition_penalty``, ``no_repeat_ngram_size`` and ``return_logprobs`` move the step onto ``sample_step`` as well,
 on its variant that reads the row's own history out[row, :pos] in the same launch (ops/reference.py
 ``process_logits`` is the rule; csrc/kernels/sample_penalty.hip): a logit whose token occurs in the history is

@@ -72,7 +72,7 @@ class GenerationSession:
         from ..models.gpt2 import dropout_seed
         from .generate import _check, _check_step
 
-        if kv_dtype != "bf16":
+        if kv_dtype != "bf16":  # ("fp4" gets the message of "fp8": neither cache is appended to or extended)
             raise ValueError(f"GenerationSession: kv_dtype={kv_dtype!r} is not supported (a session appends and "
                              "extends its caches, which an fp8 cache does not serve yet); use kv_dtype='bf16'")
         mesh = engine.mesh

@@ -44,6 +44,8 @@ hand kernels (the LayerNorm kernels are the same in both). The gate: hand >= lib
     strided copies it replaces at B = 16, S = 512;
   * the decode loop, eager and graph-replayed, at B = 16, ctx 512 and B = 64, ctx 1024;
   * the drift of the last-position logits after 128 greedy steps, fp8 teacher-forced on bf16's tokens.
+--kv_dtype fp4 does the same for the three dtypes bf16 / fp8 / fp4 (attention_decode_fp4, kv_quantize_rows_fp4) and
+writes --out_fp4kv; its gate: at B = 64, ctx 1024 the fp4 kernel is not slower than the bf16 kernel in any round.
 
 --rows measures only linear_rows, the projections at 65..512 rows, and writes --out_rows:
   * per-kernel windows, linear_rows against gemm_bf16 alternated over --rounds, at the five shapes and M in 65, 96, 128,
@@ -457,7 +459,12 @@ def fp8_cache_like(*shape):
     return q | (torch.randint(0, 2, shape, device=DEV, dtype=torch.uint8) << 7)
 
 
-def bench_fp8_kernels(rounds, reps, emit):
+def fp4_cache_like(*shape):
+    """Random e2m1 nibbles (every code is a finite value)."""
+    return torch.randint(0, 256, shape, device=DEV, dtype=torch.uint8)
+
+
+def bench_fp8_kernels(rounds, reps, emit, fp4=False):
     """attention_decode_fp8 next to attention_decode (operands as in bench_kernels; 66 against 128 bytes per row and
     operand), and kv_quantize_rows next to the two strided copies it replaces in prefill."""
     K = _native.kernels()
@@ -473,10 +480,18 @@ def bench_fp8_kernels(rounds, reps, emit):
         ve = torch.randint(-8, 8, (copies, B, H, Smax), device=DEV, dtype=torch.int8)
         qkv = torch.randn(B, 3 * H * D, device=DEV, dtype=BF)
         lens = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+        if fp4:
+            k4, v4 = fp4_cache_like(copies, B, Smax, H, D // 2), fp4_cache_like(copies, B, Smax, H, D // 2)
+            ke4 = torch.randint(-8, 8, (copies, B, H, Smax, 2), device=DEV, dtype=torch.int8)
+            ve4 = torch.randint(-8, 8, (copies, B, H, Smax, 2), device=DEV, dtype=torch.int8)
         fns = {"attention_decode": lambda i: K.attention_decode(qkv, kc[i % copies], vc[i % copies], lens, 0.125, Smax),
                "attention_decode_fp8": lambda i: K.attention_decode_fp8(qkv, k8[i % copies], ke[i % copies],
                                                                         v8[i % copies], ve[i % copies], lens, 0.125,
                                                                         Smax)}
+        if fp4:
+            fns["attention_decode_fp4"] = lambda i: K.attention_decode_fp4(qkv, k4[i % copies], ke4[i % copies],
+                                                                           v4[i % copies], ve4[i % copies], lens,
+                                                                           0.125, Smax)
         for fn in fns.values():
             window(fn, copies)
         us = {k: [] for k in fns}
@@ -484,14 +499,22 @@ def bench_fp8_kernels(rounds, reps, emit):
             for kname, fn in fns.items():  # alternated
                 ms = window(fn, reps)
                 us[kname].append(round(ms * 1e3, 2))
-                nbytes = B * (ctx + 1) * H * 2 * (D * 2 if kname == "attention_decode" else D + 1)
+                row_bytes = {"attention_decode": D * 2, "attention_decode_fp8": D + 1, "attention_decode_fp4": D // 2 + 2}
+                nbytes = B * (ctx + 1) * H * 2 * row_bytes[kname]
                 emit({"kernel": kname, "B": B, "H": H, "ctx": ctx, "round": r, "us": us[kname][-1],
                       "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1), "bytes": nbytes, "copies": copies})
         rec = {"summary": "attention_decode_fp8 vs attention_decode", "B": B, "ctx": ctx,
                "bf16_us": us["attention_decode"], "fp8_us": us["attention_decode_fp8"]}
+        if fp4:
+            rec["summary"], rec["fp4_us"] = "attention_decode_fp4 vs attention_decode_fp8 vs attention_decode", \
+                us["attention_decode_fp4"]
         if (B, ctx) == (64, 1024):
-            gate = all(f <= b for f, b in zip(us["attention_decode_fp8"], us["attention_decode"]))
-            rec["gate_fp8_not_slower_every_round"] = bool(gate)
+            kv = "fp4" if fp4 else "fp8"
+            gate = all(f <= b for f, b in zip(us[f"attention_decode_{kv}"], us["attention_decode"]))
+            rec[f"gate_{kv}_not_slower_every_round"] = bool(gate)
+            if fp4:
+                rec["target_fp4_not_slower_than_fp8"] = all(
+                    f <= g for f, g in zip(us["attention_decode_fp4"], us["attention_decode_fp8"]))
             ok = ok and gate
         emit(rec)
         del kc, vc, k8, v8, ke, ve
@@ -507,6 +530,10 @@ def bench_fp8_kernels(rounds, reps, emit):
         vc.copy_(qkv[..., 2 * C:].view(B, S, H, D))
 
     fns = {"two copy_": copies2, "kv_quantize_rows": lambda i: K.kv_quantize_rows(qkv, k8, ke, v8, ve, S)}
+    if fp4:
+        k4, v4 = (torch.empty(B, S, H, D // 2, device=DEV, dtype=torch.uint8) for _ in range(2))
+        ke4, ve4 = (torch.empty(B, H, S, 2, device=DEV, dtype=torch.int8) for _ in range(2))
+        fns["kv_quantize_rows_fp4"] = lambda i: K.kv_quantize_rows_fp4(qkv, k4, ke4, v4, ve4, S)
     for fn in fns.values():
         window(fn, 10)
     for r in range(rounds):
@@ -526,6 +553,8 @@ def run_kv_loop(engine, B, ctx, steps, kv_dtype, ses=None):
         for t in c.k + c.v:
             if kv_dtype == "fp8":
                 t.copy_(fp8_cache_like(*t.shape))
+            elif kv_dtype == "fp4":
+                t.copy_(fp4_cache_like(*t.shape))
             else:
                 t.normal_()
         for t in (c.ke or []) + (c.ve or []):
@@ -549,9 +578,9 @@ def run_kv_loop(engine, B, ctx, steps, kv_dtype, ses=None):
 
 
 @torch.no_grad()
-def bench_fp8_loop(engine, B, ctx, steps, rounds, emit):
+def bench_fp8_loop(engine, B, ctx, steps, rounds, emit, kvs=("bf16", "fp8")):
     ctx = min(ctx, engine.stages[0].cfg.block_size - steps)
-    forms = [(kv, g) for g in (False, True) for kv in ("bf16", "fp8")]
+    forms = [(kv, g) for g in (False, True) for kv in kvs]
     ses = {}
     for kv, g in forms:
         if g:
@@ -572,14 +601,14 @@ def bench_fp8_loop(engine, B, ctx, steps, rounds, emit):
 
 
 @torch.no_grad()
-def fp8_drift(engine, B, S0, steps, emit):
+def fp8_drift(engine, B, S0, steps, emit, kvq="fp8"):
     """Last-position logits of kv_dtype fp8 against bf16 after `steps` greedy steps, the fp8 run teacher-forced on the
     bf16 run's tokens (seeded weights, one prompt batch): a measured figure, not a bound."""
     stages = [engine.stages[s] for s in range(engine.P)]
     V = stages[0].cfg.vocab_size
     prompts = torch.randint(0, V, (B, S0), device=DEV, generator=torch.Generator(device=DEV).manual_seed(1))
     logits, toks = {}, []
-    for kv in ("bf16", "fp8"):
+    for kv in ("bf16", kvq):
         caches = [st.new_cache(B, S0 + steps, kv_dtype=kv) for st in stages]
         x = prompts
         for st, c in zip(stages, caches):
@@ -591,29 +620,33 @@ def fp8_drift(engine, B, S0, steps, emit):
             for st, c in zip(stages, caches):
                 x = st.decode_step(x, c)
         logits[kv] = x[:, :V].float()
-    d = logits["fp8"] - logits["bf16"]
-    emit({"summary": "fp8 KV drift", "B": B, "prompt": S0, "steps": steps,
+    d = logits[kvq] - logits["bf16"]
+    emit({"summary": f"{kvq} KV drift", "B": B, "prompt": S0, "steps": steps,
           "max_abs_diff": round(d.abs().max().item(), 4), "rms_diff": round(d.pow(2).mean().sqrt().item(), 5),
           "logits_rms": round(logits["bf16"].pow(2).mean().sqrt().item(), 4),
-          "argmax_agree": round((logits["fp8"].argmax(-1) == logits["bf16"].argmax(-1)).float().mean().item(), 3)})
+          "argmax_agree": round((logits[kvq].argmax(-1) == logits["bf16"].argmax(-1)).float().mean().item(), 3)})
 
 
 def main_fp8kv(a):
-    os.makedirs(os.path.dirname(a.out_fp8kv) or ".", exist_ok=True)
-    with open(a.out_fp8kv, "w") as f:
+    fp4 = a.kv_dtype == "fp4"
+    out = a.out_fp4kv if fp4 else a.out_fp8kv
+    os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+    with open(out, "w") as f:
         def emit(rec):
             line = json.dumps(rec)
             print(line, flush=True)
             f.write(line + "\n")
             f.flush()
 
-        ok = True if a.no_kernels else bench_fp8_kernels(a.rounds, a.reps, emit)
+        ok = True if a.no_kernels else bench_fp8_kernels(a.rounds, a.reps, emit, fp4)
         mesh = init_mesh(pp=1, schedule_kind="1f1b", rank=0, world_size=1, device=DEV)
         engine = PipelineEngine(get_model_spec("gpt2", 2), mesh, schedule_kind="1f1b", num_microbatches=1)
         engine.eval()
         for B, ctx in ((16, 512), (64, 1024)):
-            bench_fp8_loop(engine, B, ctx, a.steps, a.rounds, emit)
+            bench_fp8_loop(engine, B, ctx, a.steps, a.rounds, emit, ("bf16", "fp8", "fp4") if fp4 else ("bf16", "fp8"))
         fp8_drift(engine, 16, 64, 128, emit)
+        if fp4:
+            fp8_drift(engine, 16, 64, 128, emit, "fp4")
     return 0 if ok else 1
 
 
@@ -724,9 +757,11 @@ def main():
     ap.add_argument("--rows", action="store_true",
                     help="only linear_rows: its windows against gemm_bf16 at 65..512 rows and the decode loops at B > 64")
     ap.add_argument("--out_rows", default="profiles/linear_rows.jsonl")
-    ap.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"],
-                    help="fp8: only the fp8 KV cache's windows, loops and drift, written to --out_fp8kv")
+    ap.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8", "fp4"],
+                    help="fp8 / fp4: only the quantised KV cache's windows, loops and drift, written to --out_fp8kv / "
+                         "--out_fp4kv (fp4 measures all three dtypes)")
     ap.add_argument("--out_fp8kv", default="profiles/generate_fp8kv.jsonl")
+    ap.add_argument("--out_fp4kv", default="profiles/generate_fp4kv.jsonl")
     ap.add_argument("--B", type=int, default=16)
     ap.add_argument("--ctx", type=int, default=512)
     ap.add_argument("--rounds", type=int, default=3)
@@ -746,7 +781,7 @@ def main():
         raise SystemExit("bench_generate.py measures on the GPU; none is visible")
     if a.rows:
         return main_rows(a)
-    if a.kv_dtype == "fp8":
+    if a.kv_dtype in ("fp8", "fp4"):
         return main_fp8kv(a)
     if a.graph:
         return main_graph(a)
