@@ -95,6 +95,9 @@ def add_engine_args(parser: argparse.ArgumentParser):
     g.add_argument("--resid_pdrop", type=float, default=0.0,
                    help="gpt2, gpt2_tiny: dropout on each block's attention / MLP output before the residual add "
                         "(the three are refused with --schedule rotate and with other models)")
+    g.add_argument("--n_kv_head", type=int, default=None,
+                   help="gpt2, gpt2_tiny: grouped-query attention with this many key/value heads, a divisor of the "
+                        "model's heads (default: one per query head; refused with --tp > 1 and with other models)")
     g.add_argument("--eval_dropout", type=int, default=1,
                    help="ref_cnn: keep stage-1 dropout active in test() like the reference (1) or not (0)")
     g.add_argument("--ckpt_dir", default=None)

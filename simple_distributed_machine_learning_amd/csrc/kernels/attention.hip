@@ -68,7 +68,20 @@ struct AttnArgs {
   float scale;         // softmax scale (1/sqrt(d))
   int causal;
   DropArgs drop;       // attention-probability dropout (read by the DROP instantiations only)
+  int G;               // query heads per key/value head (read by the GQA instantiations only)
 };
+
+// Grouped-query attention (GQA instantiations): k, v, dk, dv hold H / G heads in the strides of q, and query head hh
+// reads kv head hh / G. Q, O, LSE, delta and the dropout key stay per query head, so forward and dQ only address K
+// and V elsewhere: per (batch, query head) their arithmetic is that of the kernels run on k, v expanded to H heads,
+// bit for bit. dK/dV: a workgroup owns 128 keys of one (batch, kv head) and runs the query-block loop once per query
+// head of the group, in ascending head order into the same accumulators: no atomics, fixed bits, a grid G times
+// smaller. The GQA = false instantiations are the kernels without any of it.
+template <bool GQA>
+__device__ __forceinline__ long kv_head_offset(const AttnArgs& a, int b, int hh) {
+  if constexpr (GQA) return (long)b * a.sqb + (long)(hh / a.G) * a.sqh;
+  return (long)b * a.sqb + (long)hh * a.sqh;
+}
 
 // Attention dropout (DROP instantiations; dropout_hash.h). The mask word of (query q, keys 4 k4 .. 4 k4 + 3) is
 // drop_word(rkey, q, k4) with rkey = f(seed, counter, site, layer, sample0 + b, head0 + h), computed once per wave.
@@ -90,7 +103,7 @@ __device__ __forceinline__ unsigned attn_drop_rkey(const DropArgs& d, int b, int
 // running max and the denominator l use the undropped p (LSE does not change); dropped p are zeroed before the bf16
 // pack; the 256 / (256 - T) factor multiplies the output once, together with 1 / l.
 // KBT: keys per tile (64 or 128); MINW: waves per SIMD bound
-template <int KBT, int QS, int NWV = NW, int MINW = 8 / NWV, bool DROP = false>
+template <int KBT, int QS, int NWV = NW, int MINW = 8 / NWV, bool DROP = false, bool GQA = false>
 __global__ void __launch_bounds__(64 * NWV, MINW) attn_fwd_kernel(AttnArgs a) {
   constexpr int NC = KBT / 32;  // 32-key sub-blocks per tile
   constexpr int QWV = QW * QS;  // queries per wave
@@ -106,9 +119,10 @@ __global__ void __launch_bounds__(64 * NWV, MINW) attn_fwd_kernel(AttnArgs a) {
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31,
             h = lane >> 5;
   const long qoff = (long)b * a.sqb + (long)hh * a.sqh;
+  const long koff = kv_head_offset<GQA>(a, b, hh);
   const u16* Q = a.q + qoff;
-  const u16* K = a.k + qoff;
-  const u16* V = a.v + qoff;
+  const u16* K = a.k + koff;
+  const u16* V = a.v + koff;
   const int q0w = qb * QBW + w * QWV;  // this wave's first query
   int qi[QS];                          // this lane's query in each sub-block
   // Q fragments (B operand of S^T = K Q^T): element j = Q[qi][16t + 8h + j]
@@ -274,7 +288,9 @@ constexpr int BQ = 64;  // queries per iteration (backward)
 // MFMAs, so the LDS reads per MFMA halve and each wave carries two independent accumulation chains)
 // DROP: M regenerated from the hash. dV += dO^T (M o P), the 256 / (256 - T) factor applied once at the end;
 // dP_eff = M o dP * factor; dS = P (dP_eff - delta), delta = rowsum(dO * O) with the dropped O.
-template <int NKT, bool DROP = false>
+// GQA: bh runs over (batch, kv head); the query-block loop runs once per query head hh of the group (Q, dO, LSE,
+// delta and the dropout key are that head's), all into the same dv / dk, which are stored once.
+template <int NKT, bool DROP = false, bool GQA = false>
 __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(AttnArgs a) {
   constexpr int KW = QW * NKT;  // keys per wave
   constexpr int KBW = KW * NW;  // keys per workgroup
@@ -285,11 +301,11 @@ __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(At
   const int blk = xcd_block(blockIdx.x, gridDim.x);
   const int bh = blk / nkb;
   const int kb = blk % nkb;
-  const int b = bh / a.H, hh = bh % a.H;
+  const int nkv = GQA ? a.H / a.G : a.H;  // heads of k / v
+  const int b = bh / nkv, hk = bh % nkv;
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31,
             h = lane >> 5;
-  const long off = (long)b * a.sqb + (long)hh * a.sqh;
-  const long ooff = (long)b * a.sob + (long)hh * a.soh;
+  const long off = (long)b * a.sqb + (long)hk * a.sqh;  // k, v, dk, dv
   const int k0w = kb * KBW + w * KW;
   int kj[NKT];  // this lane's keys (column of S, dP, dV^T, dK^T), one per key tile
   bf16x8 kf[NKT][4], vf[NKT][4];  // B operands: K[kj][16t + 8h + j], V[kj][...]
@@ -309,24 +325,31 @@ __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(At
   const float sl2 = a.scale * LOG2E;
   unsigned kkey[NKT];  // DROP: row key ^ this lane's key group term
   float dsc = 1.f;
-  if constexpr (DROP) {
-    const unsigned rkey = attn_drop_rkey(a.drop, b, hh);
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) kkey[kt] = rkey ^ ((unsigned)(kj[kt] >> 2) * 0x85EBCA77u);
-    dsc = drop_scale(a.drop.T);
-  }
+  if constexpr (DROP) dsc = drop_scale(a.drop.T);
   f32x16 dv[NKT][2], dk[NKT][2];
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
     for (int d = 0; d < 2; ++d) dv[kt][d] = dk[kt][d] = zero16();
   const int qstart = a.causal ? (kb * KBW) / BQ * BQ : 0;
-  const float* LSE = a.lse + (long)bh * a.S;
-  const float* DEL = a.delta + (long)bh * a.S;
+  // the query head of the pass below: its Q, dO, LSE, delta and dropout key
+  long qoff, ooff;
+  const float *LSE, *DEL;
+  auto set_head = [&](int hh) {
+    qoff = (long)b * a.sqb + (long)hh * a.sqh;
+    ooff = (long)b * a.sob + (long)hh * a.soh;
+    LSE = a.lse + ((long)b * a.H + hh) * a.S;
+    DEL = a.delta + ((long)b * a.H + hh) * a.S;
+    if constexpr (DROP) {
+      const unsigned rkey = attn_drop_rkey(a.drop, b, hh);
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) kkey[kt] = rkey ^ ((unsigned)(kj[kt] >> 2) * 0x85EBCA77u);
+    }
+  };
   TileRegs<TR> qr, dr;
   float lr = 0.f, dlr = 0.f;
   auto load = [&](int q0) {
-    tile_load(qr, a.q + off, a.sqs, q0, a.S);
+    tile_load(qr, a.q + qoff, a.sqs, q0, a.S);
     tile_load(dr, a.dout + ooff, a.sos, q0, a.S);
     if (threadIdx.x < BQ) {
       const int qi = q0 + threadIdx.x;
@@ -342,73 +365,78 @@ __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(At
       Dl[bi][threadIdx.x] = dlr;
     }
   };
-  if (qstart < a.S) {
-    load(qstart);
-    store(0);
-  }
-  __syncthreads();
-  int buf = 0;
-  for (int q0 = qstart; q0 < a.S; q0 += BQ, buf ^= 1) {
-    const bool more = q0 + BQ < a.S;
-    if (more) load(q0 + BQ);
-    if (!(a.causal && q0 + BQ - 1 < k0w)) {  // else: all these queries precede this wave's keys
-      const u16* Qt = Qs[buf];
-      const u16* Dt = Ds[buf];
-      // only the causal diagonal needs a mask: rows past S are zero-filled Q/dO (their P and dS
-      // terms multiply zero rows), and lanes with kj >= S are never stored
-      const bool edge = a.causal && q0 < k0w + KW - 1;
-      // (NKT == 2: the two 32-query sub-blocks one after the other; unrolled, hipcc overlapped their score
-      // registers and spilled)
+  const int ng = GQA ? a.G : 1;  // query heads that read this kv head, ascending: hk ng .. hk ng + ng - 1
+  for (int g = 0; g < ng; ++g) {  // (every pass ends behind a barrier, so the next may refill buffer 0)
+    set_head(hk * ng + g);
+    if (qstart < a.S) {
+      load(qstart);
+      store(0);
+    }
+    __syncthreads();
+    int buf = 0;
+    for (int q0 = qstart; q0 < a.S; q0 += BQ, buf ^= 1) {
+      const bool more = q0 + BQ < a.S;
+      if (more) load(q0 + BQ);
+      if (!(a.causal && q0 + BQ - 1 < k0w)) {  // else: all these queries precede this wave's keys
+        const u16* Qt = Qs[buf];
+        const u16* Dt = Ds[buf];
+        // only the causal diagonal needs a mask: rows past S are zero-filled Q/dO (their P and dS
+        // terms multiply zero rows), and lanes with kj >= S are never stored
+        const bool edge = a.causal && q0 < k0w + KW - 1;
+        // (NKT == 2: the two 32-query sub-blocks one after the other; unrolled, hipcc overlapped their score
+        // registers and spilled)
 #pragma unroll (NKT == 1 ? 2 : 1)
-      for (int c = 0; c < 2; ++c) {  // 32-query sub-blocks
-        f32x16 s[NKT], dp[NKT];
+        for (int c = 0; c < 2; ++c) {  // 32-query sub-blocks
+          f32x16 s[NKT], dp[NKT];
 #pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) s[kt] = dp[kt] = zero16();
+          for (int kt = 0; kt < NKT; ++kt) s[kt] = dp[kt] = zero16();
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const bf16x8 qa = rowf(Qt, 32 * c + r, t, h), da = rowf(Dt, 32 * c + r, t, h);
-#pragma unroll
-          for (int kt = 0; kt < NKT; ++kt) {
-            s[kt] = mfma(qa, kf[kt][t], s[kt]);
-            dp[kt] = mfma(da, vf[kt][t], dp[kt]);
-          }
-        }
-        // rows of s/dp are queries: q = q0 + 32c + (i&3) + 8(i>>2) + 4h
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int ql = 32 * c + (i & 3) + 8 * (i >> 2) + 4 * h;
-          const float lq = Ls[buf][ql], dq = Dl[buf][ql];
-#pragma unroll
-          for (int kt = 0; kt < NKT; ++kt) {
-            float p = ex2(s[kt][i] * sl2 - lq);
-            if (edge && kj[kt] > q0 + ql) p = 0.f;
-            if constexpr (DROP) {
-              const unsigned wd = drop_fmix32(kkey[kt] ^ ((unsigned)(q0 + ql) * 0x9E3779B1u));
-              const bool keep = drop_byte(wd, kj[kt] & 3) >= a.drop.T;
-              s[kt][i] = keep ? p : 0.f;
-              dp[kt][i] = p * ((keep ? dp[kt][i] * dsc : 0.f) - dq);
-            } else {
-              s[kt][i] = p;
-              dp[kt][i] = p * (dp[kt][i] - dq);  // dS (scale applied to dK at the end)
-            }
-          }
-        }
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-#pragma unroll
-          for (int d = 0; d < 2; ++d) {
-            const bf16x8 dta = trf(Dt, 32 * c + 16 * st, 32 * d, lane), qta = trf(Qt, 32 * c + 16 * st, 32 * d, lane);
+          for (int t = 0; t < 4; ++t) {
+            const bf16x8 qa = rowf(Qt, 32 * c + r, t, h), da = rowf(Dt, 32 * c + r, t, h);
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) {
-              dv[kt][d] = mfma(dta, pack8(s[kt], st), dv[kt][d]);
-              dk[kt][d] = mfma(qta, pack8(dp[kt], st), dk[kt][d]);
+              s[kt] = mfma(qa, kf[kt][t], s[kt]);
+              dp[kt] = mfma(da, vf[kt][t], dp[kt]);
+            }
+          }
+          // rows of s/dp are queries: q = q0 + 32c + (i&3) + 8(i>>2) + 4h
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int ql = 32 * c + (i & 3) + 8 * (i >> 2) + 4 * h;
+            const float lq = Ls[buf][ql], dq = Dl[buf][ql];
+#pragma unroll
+            for (int kt = 0; kt < NKT; ++kt) {
+              float p = ex2(s[kt][i] * sl2 - lq);
+              if (edge && kj[kt] > q0 + ql) p = 0.f;
+              if constexpr (DROP) {
+                const unsigned wd = drop_fmix32(kkey[kt] ^ ((unsigned)(q0 + ql) * 0x9E3779B1u));
+                const bool keep = drop_byte(wd, kj[kt] & 3) >= a.drop.T;
+                s[kt][i] = keep ? p : 0.f;
+                dp[kt][i] = p * ((keep ? dp[kt][i] * dsc : 0.f) - dq);
+              } else {
+                s[kt][i] = p;
+                dp[kt][i] = p * (dp[kt][i] - dq);  // dS (scale applied to dK at the end)
+              }
+            }
+          }
+#pragma unroll
+          for (int st = 0; st < 2; ++st) {
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+              const bf16x8 dta = trf(Dt, 32 * c + 16 * st, 32 * d, lane),
+                           qta = trf(Qt, 32 * c + 16 * st, 32 * d, lane);
+#pragma unroll
+              for (int kt = 0; kt < NKT; ++kt) {
+                dv[kt][d] = mfma(dta, pack8(s[kt], st), dv[kt][d]);
+                dk[kt][d] = mfma(qta, pack8(dp[kt], st), dk[kt][d]);
+              }
             }
           }
         }
       }
+      if (more) store(buf ^ 1);
+      __syncthreads();
     }
-    if (more) store(buf ^ 1);
-    __syncthreads();
   }
   // dV^T / dK^T: lane = key, register rows = d
 #pragma unroll
@@ -439,7 +467,7 @@ __global__ void __launch_bounds__(256, NKT == 1 ? 2 : 1) attn_bwd_dkdv_kernel(At
 //   dS^T = P^T (dP^T - delta[q])
 //   dQ^T[d][q] += K^T[d][k] dS^T[k][q]   (A = K^T by transposed reads, B = dS^T registers)
 // DROP: dS^T = P^T (M o dP^T * 256 / (256 - T) - delta[q]), M regenerated from the hash (one word per four keys)
-template <bool DROP = false>
+template <bool DROP = false, bool GQA = false>
 __global__ void __launch_bounds__(256, 2) attn_bwd_dq_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) u16 Ks[2][TR * HD];
   __shared__ __attribute__((aligned(16))) u16 Vs[2][TR * HD];
@@ -487,9 +515,10 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_kernel(AttnArgs a) {
   }
   f32x16 dq[2] = {zero16(), zero16()};
   const int kend = a.causal ? min(a.S, qb * QB + QB) : a.S;
+  const long koff = kv_head_offset<GQA>(a, b, hh);
   TileRegs<TR> kr, vr;
-  tile_load(kr, a.k + off, a.sqs, 0, a.S);
-  tile_load(vr, a.v + off, a.sqs, 0, a.S);
+  tile_load(kr, a.k + koff, a.sqs, 0, a.S);
+  tile_load(vr, a.v + koff, a.sqs, 0, a.S);
   tile_store(Ks[0], kr);
   tile_store(Vs[0], vr);
   __syncthreads();
@@ -497,8 +526,8 @@ __global__ void __launch_bounds__(256, 2) attn_bwd_dq_kernel(AttnArgs a) {
   for (int k0 = 0; k0 < kend; k0 += KB, buf ^= 1) {
     const bool more = k0 + KB < kend;
     if (more) {
-      tile_load(kr, a.k + off, a.sqs, k0 + KB, a.S);
-      tile_load(vr, a.v + off, a.sqs, k0 + KB, a.S);
+      tile_load(kr, a.k + koff, a.sqs, k0 + KB, a.S);
+      tile_load(vr, a.v + koff, a.sqs, k0 + KB, a.S);
     }
     if (!(a.causal && k0 > q0w + QW - 1)) {
       const u16* Kt = Ks[buf];
@@ -588,6 +617,7 @@ AttnArgs make_args(const AttnShape& s) {
   a.scale = s.scale;
   a.causal = s.causal;
   a.drop = s.drop;
+  a.G = (s.Hkv > 0 && s.Hkv < s.H && s.H % s.Hkv == 0) ? s.H / s.Hkv : 1;
   return a;
 }
 
@@ -598,6 +628,14 @@ void attention_set_fwd_kb(int kb) { g_fwd_kb = kb; }
 
 void attention_fwd_bf16(const AttnShape& s, hipStream_t stream) {
   AttnArgs a = make_args(s);
+  if (a.G > 1) {  // grouped k / v: the default tile shape (the knobs below choose among the G = 1 kernels only)
+    const dim3 grid(((s.S + QB - 1) / QB) * s.B * s.H);
+    if (s.drop.T)
+      hipLaunchKernelGGL((attn_fwd_kernel<64, 1, NW, 8 / NW, true, true>), grid, dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL((attn_fwd_kernel<64, 1, NW, 8 / NW, false, true>), grid, dim3(256), 0, stream, a);
+    return;
+  }
   if (s.drop.T) {  // dropout: the default tile shape with the mask compiled in (ATTN_FWD_QS, ATTN_OCC and
                    // attention_set_fwd_kb choose among the kernels without dropout only)
     const int nqb = (s.S + QB - 1) / QB;
@@ -632,6 +670,17 @@ void attention_bwd_bf16(const AttnShape& s, hipStream_t stream) {
   const int nb = (s.S + QB - 1) / QB;
   // dQ first: it computes delta = rowsum(dO * O) for its own queries and writes it for dK/dV
   const bool run_dq = s.bwd_parts & 1, run_dkdv = s.bwd_parts & 2;
+  if (a.G > 1) {  // grouped k / v: the default shapes; dK/dV's grid runs over the kv heads
+    const dim3 gq(nb * s.B * s.H), gk(nb * s.B * (s.H / a.G));
+    if (s.drop.T) {
+      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), gq, dim3(256), 0, stream, a);
+      if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<1, true, true>), gk, dim3(256), 0, stream, a);
+    } else {
+      if (run_dq) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, dim3(256), 0, stream, a);
+      if (run_dkdv) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<1, false, true>), gk, dim3(256), 0, stream, a);
+    }
+    return;
+  }
   if (s.drop.T) {  // dropout: the default shapes with the mask compiled in (the knobs below do not apply)
     if (run_dq) hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, dim3(nb * s.B * s.H), dim3(256), 0, stream, a);
     if (run_dkdv)

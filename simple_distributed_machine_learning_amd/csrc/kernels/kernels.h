@@ -482,6 +482,9 @@ struct AttnShape {
   void *out = nullptr, *dq = nullptr, *dk = nullptr, *dv = nullptr;
   float *lse = nullptr, *delta = nullptr;
   int B = 0, H = 0, S = 0;
+  int Hkv = 0;  // grouped-query attention: k / v (dk / dv) hold Hkv heads, a divisor of H, in the same strides, and
+                // query head h reads kv head h / (H / Hkv). 0 or H: one kv head per query head, the kernels as they
+                // were. A grouped call runs the default tile shapes, as a dropout call does.
   long sqb = 0, sqh = 0, sqs = 0, sob = 0, soh = 0, sos = 0;
   float scale = 1.f;
   int causal = 1;
@@ -522,6 +525,14 @@ void attention_decode_bf16(const AttnDecodeArgs& a, hipStream_t stream);
 // The second launch of the two-launch form alone: the slots of every (b, h) in chunk order to out (reads lens, ws_ml,
 // ws_o, B, H, Smax, max_chunks of `a`). attention_decode_fp8.hip's chunks write attn_chunk.h's slots and call this.
 void attention_decode_combine(const AttnDecodeArgs& a, hipStream_t stream);
+// attention_decode_bf16 on a grouped cache (attention_decode_gqa.hip): a.H query heads share Hkv = a.H / G key/value
+// heads, query head h reading kv head h / G. qkv [B][ldq] = (q: 64 H | k: 64 Hkv | v: 64 Hkv); the caches are
+// [b][s][Hkv][64] in a's strides; workspace and out as attention_decode_bf16 takes them, per query head. One wave
+// loads a 64-key chunk of one (sample, kv head) once and serves the group's G queries; the second launch is
+// attention_decode_combine. Bit for bit attention_decode_bf16 on the cache and qkv expanded to H heads. No one-launch
+// form (a.tickets must be null). G in {2, 3, 4, 6, 12}: attention_decode_gqa_supported.
+bool attention_decode_gqa_supported(int G);
+void attention_decode_gqa_bf16(const AttnDecodeArgs& a, int Hkv, hipStream_t stream);
 // ---- fp8 KV cache (kv_fp8.h, kv_quantize.hip, attention_decode_fp8.hip; ops/decode.py kv_quantize is the format) ----
 // A cache row (sample, key, head) is 64 OCP e4m3 bytes and one int8 exponent e: value = e4m3(byte) * 2^e, e the
 // smallest integer with amax * 2^-e <= 448, clamped to [-120, 120], 0 for an all-zero row. k8 / v8 [B][Smax][H][64]

@@ -1797,15 +1797,18 @@ sdml::DropArgs attn_drop_args(const torch::Tensor& q, int64_t drop_t, int64_t dr
 
 // q, k, v: [B, S, H, 64] bf16 views sharing strides (d contiguous), e.g. slices of the fused
 // qkv projection. Returns (out [B, S, H, 64] contiguous, lse fp32 [B*H*S]).
+// Grouped-query attention: k and v may be [B, S, Hkv, 64] with Hkv dividing H (the same strides: narrower blocks of
+// the same rows); query head h reads kv head h / (H / Hkv), on the grouped instantiations of the kernels.
 std::tuple<torch::Tensor, torch::Tensor> attention_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, double scale,
                                                        bool causal, int64_t drop_t, int64_t drop_seed,
                                                        c10::optional<torch::Tensor> drop_ctr, int64_t drop_site_layer,
                                                        int64_t sample0, int64_t head0) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16, "attention: bf16 device tensors");
   TORCH_CHECK(q.dim() == 4 && q.size(3) == 64 && q.stride(3) == 1, "attention: [B, S, H, 64] with contiguous d");
-  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes() && k.strides() == q.strides() &&
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes() && k.size(0) == q.size(0) && k.size(1) == q.size(1) &&
+                  k.size(3) == 64 && k.size(2) >= 1 && q.size(2) % k.size(2) == 0 && k.strides() == q.strides() &&
                   v.strides() == q.strides(),
-              "attention: q/k/v must share shape and strides");
+              "attention: q/k/v must share shape and strides (k / v may hold n_kv_head heads, a divisor of q's)");
   TORCH_CHECK(q.stride(2) % 8 == 0 && q.stride(1) % 8 == 0 && (reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(k.data_ptr()) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(v.data_ptr()) & 15) == 0,
@@ -1821,6 +1824,7 @@ std::tuple<torch::Tensor, torch::Tensor> attention_fwd(torch::Tensor q, torch::T
   a.lse = lse.data_ptr<float>();
   a.B = B;
   a.H = H;
+  a.Hkv = k.size(2);
   a.S = S;
   a.sqb = q.stride(0);
   a.sqs = q.stride(1);
@@ -1843,6 +1847,10 @@ void attention_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Ten
   TORCH_CHECK(out.is_contiguous() && dout.is_contiguous() && out.sizes() == dout.sizes(), "attention bwd: out/dout");
   TORCH_CHECK(dq.strides() == q.strides() && dk.strides() == q.strides() && dv.strides() == q.strides(),
               "attention bwd: grads must use the q/k/v strides");
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes() && dq.sizes() == q.sizes() && dk.sizes() == k.sizes() &&
+                  dv.sizes() == k.sizes() && k.size(2) >= 1 && q.size(2) % k.size(2) == 0 &&
+                  k.strides() == q.strides() && v.strides() == q.strides(),
+              "attention bwd: k / v (and dk / dv) hold q's heads or n_kv_head heads, a divisor of them");
   const int64_t B = q.size(0), S = q.size(1), H = q.size(2);
   // parts / delta (timing tools): the dQ kernel (1) writes delta = rowsum(dO * O), the dK/dV kernel (2) reads it; a
   // call that runs only one of them shares delta with the other through the caller's buffer
@@ -1871,6 +1879,7 @@ void attention_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Ten
   a.delta = delta.data_ptr<float>();
   a.B = B;
   a.H = H;
+  a.Hkv = k.size(2);
   a.S = S;
   a.sqb = q.stride(0);
   a.sqs = q.stride(1);
@@ -2158,6 +2167,41 @@ torch::Tensor attention_decode(torch::Tensor qkv, torch::Tensor k_cache, torch::
   a.ldq = qkv.stride(0), a.sb = k_cache.stride(0), a.ss = k_cache.stride(1), a.sh = k_cache.stride(2);
   a.scale = (float)scale;
   sdml::attention_decode_bf16(a, cur_stream());
+  return out;
+}
+
+// attention_decode on a grouped cache (attention_decode_gqa.hip): n_head query heads over the cache's Hkv = n_head / G
+// key/value heads. qkv [B, 64 (n_head + 2 Hkv)] = (q | k | v), k_cache / v_cache [B, Smax, Hkv, 64]; lens and n_keys
+// as attention_decode takes them. Returns [B, 64 n_head] with attention_decode's bits on the expanded cache.
+torch::Tensor attention_decode_gqa(torch::Tensor qkv, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor lens,
+                                   int64_t n_head, double scale, int64_t n_keys) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1,
+              "attention_decode_gqa: qkv must be a [B, C + 2 Ckv] bf16 device tensor with unit column stride");
+  check_kv_pair("attention_decode_gqa", k_cache, v_cache, qkv,
+                "k_cache / v_cache must be bf16 device tensors [B, Smax, Hkv, 64] of one layout",
+                "16-byte aligned rows required");
+  const int64_t B = qkv.size(0), Smax = k_cache.size(1), Hkv = k_cache.size(2), H = n_head;
+  TORCH_CHECK(Hkv >= 1 && H > Hkv && H % Hkv == 0 && sdml::attention_decode_gqa_supported((int)(H / Hkv)),
+              "attention_decode_gqa: n_head = ", H, " over n_kv_head = ", Hkv,
+              " key/value heads: the group size n_head / n_kv_head must be one of 2, 3, 4, 6, 12");
+  TORCH_CHECK(k_cache.size(0) == B && qkv.size(1) == 64 * (H + 2 * Hkv), "attention_decode_gqa: qkv ", qkv.sizes(),
+              " does not match n_head = ", H, " and a ", k_cache.sizes(), " cache");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0 && aligned16(qkv), "attention_decode_gqa: 16-byte aligned rows required");
+  sdml::AttnDecodeArgs a;
+  a.lens = device_i32("attention_decode_gqa", "lens", "B", lens, B, qkv);
+  TORCH_CHECK(n_keys >= 1 && n_keys <= Smax, "attention_decode_gqa: the cache is full: ", n_keys,
+              " keys with the new one, ", Smax, " rows (lens[b] + 1 <= n_keys <= Smax)");
+  TORCH_CHECK(B >= 1 && B <= 65535 && H <= 65535, "attention_decode_gqa: batch / heads out of the grid's range");
+  a.max_chunks = sdml::attention_decode_chunks((int)n_keys);
+  auto out = torch::empty({B, H * 64}, qkv.options());
+  auto ws = torch::empty({B * H * a.max_chunks * 66}, qkv.options().dtype(torch::kFloat32));
+  a.qkv = qkv.data_ptr(), a.k_cache = k_cache.data_ptr(), a.v_cache = v_cache.data_ptr(), a.out = out.data_ptr();
+  a.ws_o = ws.data_ptr<float>();
+  a.ws_ml = a.ws_o + B * H * a.max_chunks * 64;
+  a.B = (int)B, a.H = (int)H, a.Smax = (int)Smax;
+  a.ldq = qkv.stride(0), a.sb = k_cache.stride(0), a.ss = k_cache.stride(1), a.sh = k_cache.stride(2);
+  a.scale = (float)scale;
+  sdml::attention_decode_gqa_bf16(a, (int)Hkv, cur_stream());
   return out;
 }
 
@@ -2806,6 +2850,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one new token per sample against a KV cache (bf16, d=64): writes k, v at row lens[b], returns [B, C]",
         py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("scale"), py::arg("n_keys"),
         py::arg("tickets") = py::none());
+  m.def("attention_decode_gqa", &attention_decode_gqa,
+        "attention_decode on a grouped cache [B, Smax, Hkv, 64] (n_head = G Hkv query heads, qkv = q | k | v with "
+        "narrow k, v): writes k, v at row lens[b], returns [B, 64 n_head] with attention_decode's bits",
+        py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("n_head"), py::arg("scale"),
+        py::arg("n_keys"));
   m.def("attention_decode_fp8", &attention_decode_fp8,
         "attention_decode on an fp8 KV cache (e4m3 bytes [B, Smax, H, 64] + int8 row exponents [B, H, Smax]): "
         "quantises and writes k, v at row lens[b], returns [B, C]",

@@ -22,7 +22,9 @@ step streams; the plain loop and ``--graph`` only), ``--kv_dtype fp4`` as e2m1 n
 channels (a quarter of the bytes, a much coarser rounding); the event carries ``kv_dtype``. ``--repetition_penalty THETA``
 and ``--no_repeat_ngram_size N`` make the sampler read the row's own history (parallel/generate.py; not with ``--lookup``
 or ``--num_beams``); ``--logprobs`` prints `` logprob=<sum>`` after a row's tokens, the model's log-probability of what
-the row generated. The event carries the two knobs.
+the row generated. The event carries the two knobs. ``--n_kv_head HKV`` loads a checkpoint trained with grouped-query
+attention (``train --n_kv_head HKV``): the KV cache holds HKV heads; the plain loop and ``--graph`` serve it, every
+other mode refuses it by name. The event carries ``n_kv_head``.
 """
 from __future__ import annotations
 
@@ -59,6 +61,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--timeout", type=float, default=600.0, help="process-group timeout (s)")
     g.add_argument("--dtype", default="auto", choices=["auto", "fp32", "bf16"])
     g.add_argument("--seq_len", type=int, default=None, help="sequence length of --prompt_from_data's sequences")
+    g.add_argument("--n_kv_head", type=int, default=None,
+                   help="the key/value heads the checkpoint was trained with (grouped-query attention; default: one per "
+                        "query head). Below the model's heads: the plain loop and --graph only, --kv_dtype bf16")
     g.add_argument("--seed", type=int, default=1, help="run seed: keys the sampler's noise")
     g.add_argument("--data_seed", type=int, default=1234)
     g.add_argument("--ckpt_dir", default=None, help="checkpoint to load (train --ckpt_dir); none: initial weights")
@@ -170,7 +175,11 @@ def run(args) -> dict:
                      world_size=args.world_size, device=device, tp=args.tp)
     dt = {"fp32": torch.float32, "bf16": torch.bfloat16}.get(args.dtype)
     kw = {"dtype": dt} if dt is not None and args.model == "gpt2_tiny" else {}
-    spec = get_model_spec(args.model, stages, seq_len=args.seq_len, **kw)
+    try:
+        spec = get_model_spec(args.model, stages, seq_len=args.seq_len, n_kv_head=args.n_kv_head, **kw)
+    except ValueError as e:  # (--n_kv_head that does not divide the heads)
+        shutdown(mesh)
+        raise SystemExit(str(e))
     if dt is not None and spec.param_dtype != dt:
         raise SystemExit(f"--dtype {args.dtype} is not supported for --model {args.model}")
     engine = PipelineEngine(spec, mesh, schedule_kind=args.schedule, num_microbatches=1, seed=args.seed)
@@ -212,7 +221,8 @@ def run(args) -> dict:
                     top_p=args.top_p, graph=bool(args.graph), lookup=args.lookup, lookup_ngram=args.lookup_ngram,
                     steps=steps, tokens_per_step=None if not steps else n_new / steps,
                     num_samples=args.num_samples, num_beams=args.num_beams, kv_dtype=args.kv_dtype,
-                    repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size)
+                    repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
+                    n_kv_head=args.n_kv_head)
     return {"tokens": rows, "engine": engine, "mesh": mesh, "seconds": dt_s}
 
 

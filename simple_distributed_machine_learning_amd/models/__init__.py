@@ -20,6 +20,10 @@ def get_model_spec(name: str, num_stages: int = None, **kw) -> ModelSpec:
     if name not in ("gpt2", "gpt2_tiny") and any(pdrop.values()):
         on = ", ".join(f"--{k}" for k, v in pdrop.items() if v)
         raise ValueError(f"{on}: GPT-2 dropout needs a GPT-2 model (gpt2, gpt2_tiny), not {name!r}")
+    n_kv_head = kw.get("n_kv_head")
+    if name not in ("gpt2", "gpt2_tiny") and n_kv_head is not None:
+        raise ValueError(f"--n_kv_head: grouped-query attention needs a GPT-2 model (gpt2, gpt2_tiny), not {name!r}")
+    pdrop["n_kv_head"] = n_kv_head  # (GPT2Config's keyword arguments from here on)
     if name == "mlp":
         return mlp_spec(MLP_DIMS, n, "mlp")
     if name == "mlp4x1024":

@@ -37,7 +37,7 @@ from ..ops.linear import Linear, _w_padded, linear, lm_head, mlp_gelu
 from ..ops.reference import (DROP_SITE_ATTN, DROP_SITE_EMBD, DROP_SITE_RESID_ATTN, DROP_SITE_RESID_MLP,
                              dropout_threshold)
 from ..ops.transformer import (Drop, LayerNorm, add_layer_norm, causal_attention, cross_entropy_sum, dropout_add,
-                               embedding, gelu, layer_norm_pass)
+                               embedding, gelu, layer_norm_pass, split_gqa)
 from ..parallel.tp import TPContext, column_slice, copy_to_tp, reduce_from_tp, shard_parameter
 
 
@@ -52,8 +52,24 @@ class GPT2Config:
     embd_pdrop: Optional[float] = None   # on wte[tok] + wpe[pos]
     attn_pdrop: Optional[float] = None   # on the attention probabilities
     resid_pdrop: Optional[float] = None  # on each block's attention and MLP output before the residual add
+    # grouped-query attention: key/value heads, a divisor of n_head (None: n_head). c_attn is then C + 2 n_kv_head D
+    # wide, its output row (q: n_head D | k: n_kv_head D | v: n_kv_head D), and query head h reads kv head
+    # h // (n_head // n_kv_head); the KV cache holds n_kv_head heads
+    n_kv_head: Optional[int] = None
+
+    @property
+    def kv_heads(self) -> int:
+        return self.n_head if self.n_kv_head is None else self.n_kv_head
+
+    @property
+    def grouped(self) -> bool:
+        return self.kv_heads != self.n_head
 
     def __post_init__(self):
+        if self.n_kv_head is not None and (isinstance(self.n_kv_head, bool) or not isinstance(self.n_kv_head, int)
+                                           or self.n_kv_head < 1 or self.n_head % self.n_kv_head):
+            raise ValueError(f"GPT2Config: n_kv_head={self.n_kv_head!r} must be a positive divisor of n_head="
+                             f"{self.n_head}")
         for f in ("embd_pdrop", "attn_pdrop", "resid_pdrop"):
             if getattr(self, f) is None:
                 setattr(self, f, float(self.dropout))
@@ -76,9 +92,10 @@ def dropout_seed(seed: int) -> int:
 class CausalSelfAttention(nn.Module):
     def __init__(self, cfg: GPT2Config):
         super().__init__()
-        self.c_attn = Linear(cfg.n_embd, 3 * cfg.n_embd)
+        self.c_attn = Linear(cfg.n_embd, cfg.n_embd + 2 * cfg.kv_heads * (cfg.n_embd // cfg.n_head))
         self.c_proj = Linear(cfg.n_embd, cfg.n_embd)
         self.n_head = cfg.n_head
+        self.n_kv_head = cfg.n_kv_head if cfg.grouped else None  # None: the calls below are the ones they always were
         self.head0 = 0  # global index of this rank's first head
         self.tp: TPContext = None
 
@@ -100,6 +117,8 @@ class CausalSelfAttention(nn.Module):
         # layer and call; the mask is keyed by the global head index
         if drop is not None:
             drop = Drop(drop.T, drop.seed, drop.ctr, drop.site, drop.layer, drop.sample0, self.head0)
+        if self.n_kv_head is not None:  # grouped-query attention (never tensor-parallel: shard_tp refuses)
+            return self.c_proj(causal_attention(self.c_attn(x), self.n_head, drop, n_kv_head=self.n_kv_head))
         if self.tp is None:
             return self.c_proj(causal_attention(self.c_attn(x), self.n_head, drop))
         a = causal_attention(self.c_attn(copy_to_tp(x, self.tp)), self.n_head, drop)
@@ -205,6 +224,9 @@ class GPT2Stage(PipelineStage):
         vocabulary head stay replicated."""
         if self.cfg.n_head % tp.size:
             raise ValueError(f"n_head={self.cfg.n_head} is not divisible by tp={tp.size}")
+        if self.cfg.grouped:
+            raise ValueError(f"tp={tp.size} is not supported with n_kv_head={self.cfg.n_kv_head} != n_head="
+                             f"{self.cfg.n_head}: the grouped k / v columns are not sharded yet")
         for blk in self.h.values():
             blk.attn.shard_tp(tp)
             blk.mlp.shard_tp(tp)
@@ -286,8 +308,12 @@ class GPT2Stage(PipelineStage):
             raise ValueError(f"a cache of {Smax} positions exceeds block_size={self.cfg.block_size}")
         if getattr(self, "tp", None) is not None:
             raise ValueError("generation does not run tensor-parallel stages (tp > 1)")
+        if self.cfg.grouped and kv_dtype != "bf16":
+            raise ValueError(f"new_cache: kv_dtype={kv_dtype!r} is not supported with n_kv_head={self.cfg.n_kv_head} "
+                             f"!= n_head={self.cfg.n_head} (the fp8 / fp4 decode kernels read one kv head per query "
+                             "head); use kv_dtype='bf16'")
         p = next(self.parameters())
-        H, D = self.cfg.n_head, self.cfg.n_embd // self.cfg.n_head
+        H, D = self.cfg.kv_heads, self.cfg.n_embd // self.cfg.n_head  # (a grouped cache holds n_kv_head heads)
         mk = lambda: torch.empty((B, Smax, H, D), dtype=p.dtype, device=p.device)  # noqa: E731
         n = len(self.h)
         tickets = None
@@ -306,10 +332,12 @@ class GPT2Stage(PipelineStage):
                            [mke() for _ in range(n)], [mke() for _ in range(n)])
         return KVCache([mk() for _ in range(n)], [mk() for _ in range(n)], lens, 0, Smax, tickets)
 
-    @staticmethod
-    def _bf16_cache_only(who: str, cache: "KVCache"):
+    def _bf16_cache_only(self, who: str, cache: "KVCache"):
         if cache.kv_dtype != "bf16":
             raise ValueError(f"{who}: a kv_dtype={cache.kv_dtype!r} cache is served by prefill and decode_step only")
+        if self.cfg.grouped:
+            raise ValueError(f"{who}: a grouped cache (n_kv_head={self.cfg.n_kv_head} != n_head={self.cfg.n_head}) is "
+                             "served by prefill and decode_step only")
 
     @staticmethod
     def _decode_attention(cache: "KVCache", H: int, n_keys: int, tickets=None):
@@ -335,7 +363,8 @@ class GPT2Stage(PipelineStage):
         allocation's start, stays a multiple of 16 bytes."""
         C = self.cfg.n_embd
         inner = next(iter(self.h.values())).mlp.c_fc.weight.shape[0] if len(self.h) else 4 * C
-        raw = (3 * C // 16, B * self.cfg.n_head, C // 16, inner // 16, C // 16)
+        qkv = C + 2 * self.cfg.kv_heads * (C // self.cfg.n_head)  # c_attn's width: 3 C unless grouped
+        raw = (qkv // 16, B * self.cfg.n_head, C // 16, inner // 16, C // 16)
         return tuple((v + 3) // 4 * 4 for v in raw)
 
     def _ticket_views(self, cache: "KVCache"):
@@ -432,6 +461,11 @@ class GPT2Stage(PipelineStage):
 
         def attn(i, blk, y):
             qkv = blk.attn.c_attn(y)
+            if self.cfg.grouped:  # the narrow k and v blocks into a cache of n_kv_head heads
+                _, k, v = split_gqa(qkv, H, self.cfg.n_kv_head)
+                cache.k[i][:, :S].copy_(k)
+                cache.v[i][:, :S].copy_(v)
+                return blk.attn.c_proj(causal_attention(qkv, H, n_kv_head=self.cfg.n_kv_head))
             if cache.kv_dtype == "fp4":  # (the flash kernel below still reads the prompt's unquantised k and v)
                 kv_quantize_rows_fp4(qkv, cache.k[i], cache.ke[i], cache.v[i], cache.ve[i], S)
             elif cache.kv_dtype == "fp8":

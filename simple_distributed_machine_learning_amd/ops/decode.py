@@ -23,6 +23,7 @@ LINEAR_ROWS_MAX_M = 512  # kLinearRowsMaxM
 LINEAR_ROWS_DISPATCH_M = 512  # kLinearRowsDispatchM: measured against gemm_bf16 (README.md, "linear_rows")
 ATTENTION_APPEND_MAX_T = 8  # kAttnAppendMaxT
 ATTENTION_FORK_MAX_N = 64  # kAttnForkMaxN
+ATTENTION_DECODE_GQA_GROUPS = (2, 3, 4, 6, 12)  # attention_decode_gqa_supported: n_head / n_kv_head on the kernel
 LOOKUP_MAX_DRAFTS, LOOKUP_MAX_NGRAM = 7, 8  # kLookupMaxDrafts, kLookupMaxNgram
 BEAM_MAX_K, BEAM_MAX_ROWS, BEAM_MAX_VOCAB = 8, 64, 65536  # kBeamMaxK, kBeamMaxRows, kBeamMaxVocab
 BEAM_THREADS = 1024  # beam.hip's threads per logits row
@@ -73,11 +74,14 @@ def linear_decode(x, w, b=None, gelu: bool = False, tickets=None):
 
 def attention_decode_ref(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int):
     """The twin: write the new k, v at cache row lens[b]; softmax(q K[0..lens[b]]^T / sqrt(D)) V[0..lens[b]] in fp32.
-    Rows past lens[b] are selected away (a cache from torch.empty may hold NaN patterns)."""
-    B, C3 = qkv.shape
-    C = C3 // 3
-    D = C // n_head
-    q, k, v = (qkv[:, i * C:(i + 1) * C].view(B, n_head, D) for i in range(3))
+    Rows past lens[b] are selected away (a cache from torch.empty may hold NaN patterns). A grouped cache
+    [B, Smax, Hkv, D] with Hkv < n_head: qkv is [B, (n_head + 2 Hkv) D] = (q | k | v) and query head h reads kv head
+    h // (n_head // Hkv)."""
+    B = qkv.shape[0]
+    Hkv = k_cache.shape[2]
+    D = qkv.shape[1] // (n_head + 2 * Hkv)
+    q, k, v = qkv.split((n_head * D, Hkv * D, Hkv * D), dim=1)
+    q, k, v = q.view(B, n_head, D), k.view(B, Hkv, D), v.view(B, Hkv, D)
     idx = lens.to(torch.int64)
     rows = torch.arange(B, device=qkv.device)
     k_cache[rows, idx] = k
@@ -85,6 +89,9 @@ def attention_decode_ref(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int):
     live = torch.arange(n_keys, device=qkv.device)[None, :] <= idx[:, None]  # [B, n_keys]
     kc = torch.where(live[:, :, None, None], k_cache[:, :n_keys], torch.zeros_like(k_cache[:, :n_keys])).float()
     vc = torch.where(live[:, :, None, None], v_cache[:, :n_keys], torch.zeros_like(v_cache[:, :n_keys])).float()
+    if Hkv != n_head:  # the head map
+        kc, vc = (t.repeat_interleave(n_head // Hkv, 2) for t in (kc, vc))
+    C = n_head * D
     s = torch.einsum("bhd,bshd->bhs", q.float(), kc) * (1.0 / math.sqrt(D))
     p = torch.softmax(s.masked_fill(~live[:, None, :], -math.inf), dim=-1)
     return torch.einsum("bhs,bshd->bhd", p, vc).to(qkv.dtype).reshape(B, C)
@@ -103,7 +110,13 @@ def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int, tick
     the bits are those of the call without tickets at any n_keys > max(lens). A wrong dtype, device or size is a
     RuntimeError. The bound n_keys > max(lens) cannot be checked without reading the device: if it is violated, the
     rows concerned are not written and their counters are left non-zero, so zero the tensor before using it again
-    (``decode_step`` passes Smax and zeroes its buffer every step). The torch twin ignores it."""
+    (``decode_step`` passes Smax and zeroes its buffer every step). The torch twin ignores it.
+
+    A grouped cache, ``k_cache.shape[2]`` = Hkv < n_head (grouped-query attention; Hkv must divide n_head): qkv is
+    [B, (n_head + 2 Hkv) D] = (q | k | v) and query head h reads kv head h // (n_head // Hkv). On the kernels
+    (attention_decode_gqa.hip, group sizes ``ATTENTION_DECODE_GQA_GROUPS``) a wave loads a chunk's rows once for the
+    group's queries; the output and the cache are, bit for bit, those of this function on the cache and qkv expanded
+    to n_head heads. Two launches; ``tickets`` is refused."""
     Smax = k_cache.shape[1]
     if k_cache.dtype == torch.uint8:
         raise ValueError("attention_decode: an fp8 cache goes through attention_decode_fp8, which has no one-launch "
@@ -111,6 +124,20 @@ def attention_decode(qkv, k_cache, v_cache, lens, n_head: int, n_keys: int, tick
     if not 1 <= n_keys <= Smax:
         raise ValueError(f"attention_decode: {n_keys} keys with the new one, but the cache has {Smax} rows")
     D = k_cache.shape[-1]
+    if k_cache.dim() == 4 and k_cache.shape[2] < n_head:  # a grouped cache (n_kv_head < n_head)
+        Hkv = k_cache.shape[2]
+        if tickets is not None:
+            raise ValueError("attention_decode: a grouped cache (n_kv_head < n_head) has no one-launch (tickets) form")
+        if Hkv < 1 or n_head % Hkv or qkv.shape[-1] != (n_head + 2 * Hkv) * D:
+            raise ValueError(f"attention_decode: n_kv_head={Hkv} must divide n_head={n_head} and qkv be "
+                             f"[B, (n_head + 2 n_kv_head) D], got {tuple(qkv.shape)} with D={D}")
+        if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
+            if n_head // Hkv not in ATTENTION_DECODE_GQA_GROUPS:
+                raise ValueError(f"attention_decode: n_head / n_kv_head = {n_head // Hkv} is not a group size the "
+                                 f"grouped kernel serves ({ATTENTION_DECODE_GQA_GROUPS})")
+            return kernels().attention_decode_gqa(qkv, k_cache, v_cache, lens, int(n_head), 1.0 / math.sqrt(D),
+                                                  int(n_keys))
+        return attention_decode_ref(qkv, k_cache, v_cache, lens, n_head, n_keys)
     if _hip_bf16(qkv, k_cache, v_cache) and D == 64:
         if tickets is not None:
             return kernels().attention_decode(qkv, k_cache, v_cache, lens, 1.0 / math.sqrt(D), int(n_keys), tickets)

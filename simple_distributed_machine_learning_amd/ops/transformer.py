@@ -277,10 +277,58 @@ class _FlashAttnFn(torch.autograd.Function):
         return dqkv, None, None, None
 
 
-def causal_attention(qkv, n_head: int, drop: Optional[Drop] = None):
+class _FlashAttnGqaFn(torch.autograd.Function):
+    """``_FlashAttnFn`` on a grouped projection [B, S, C + 2 Hkv D] = (q | k | v): the kernels' grouped instantiations
+    (csrc/kernels/attention.hip), k / v and their gradients as Hkv-head views of the same rows."""
+
+    @staticmethod
+    def forward(ctx, qkv, n_head: int, n_kv_head: int, scale: float, drop: Optional[Drop] = None):
+        B, S, _ = qkv.shape
+        qkv = qkv.contiguous()
+        ctx.dkw = {} if drop is None else dict(drop.kw(), head0=drop.head0)
+        ctx.heads, ctx.scale = (n_head, n_kv_head), scale
+        out, lse = kernels().attention_fwd(*split_gqa(qkv, n_head, n_kv_head), scale, True, **ctx.dkw)
+        ctx.save_for_backward(qkv, out, lse)
+        return out.view(B, S, -1)
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkv, out, lse = ctx.saved_tensors
+        dqkv = torch.empty_like(qkv)
+        kernels().attention_bwd(*split_gqa(qkv, *ctx.heads), out, gout.contiguous().view(out.shape), lse,
+                                *split_gqa(dqkv, *ctx.heads), ctx.scale, True, **ctx.dkw)
+        return dqkv, None, None, None, None
+
+
+def split_gqa(qkv, n_head: int, n_kv_head: int):
+    """The (q [.., H, D], k [.., Hkv, D], v [.., Hkv, D]) views of a grouped projection [.., (H + 2 Hkv) D]."""
+    D = qkv.shape[-1] // (n_head + 2 * n_kv_head)
+    q, k, v = qkv.split((n_head * D, n_kv_head * D, n_kv_head * D), dim=-1)
+    return q.unflatten(-1, (n_head, D)), k.unflatten(-1, (n_kv_head, D)), v.unflatten(-1, (n_kv_head, D))
+
+
+def expand_gqa(qkv, n_head: int, n_kv_head: int):
+    """The grouped projection as the [.., 3C] projection of the same attention with H key/value heads: kv head j
+    repeated for the query heads j G .. j G + G - 1 (differentiable: the gradient sums over the group)."""
+    q, k, v = split_gqa(qkv, n_head, n_kv_head)
+    G = n_head // n_kv_head
+    return torch.cat([t.flatten(-2) for t in (q, k.repeat_interleave(G, -2), v.repeat_interleave(G, -2))], -1)
+
+
+def causal_attention(qkv, n_head: int, drop: Optional[Drop] = None, n_kv_head: Optional[int] = None):
     """softmax(q k^T / sqrt(d), causal) v from a fused [B, S, 3C] projection -> [B, S, C]. ``drop``: dropout on the
     probabilities (inside the flash kernels on ROCm bf16 d = 64; elsewhere an explicit masked softmax . matmul with the
-    same mask from the torch twin)."""
+    same mask from the torch twin). ``n_kv_head`` = Hkv < n_head (a divisor of it): grouped-query attention on a
+    projection [B, S, C + 2 Hkv D] = (q | k | v), query head h reading kv head h // (n_head // Hkv). The definition is
+    this function on ``expand_gqa`` of the projection, which is what CPU, fp32 and other head widths run; the kernels
+    give its output, LSE and dQ bit for bit and sum dK / dV over the group in fp32 (docs/NUMERICS.md)."""
+    if n_kv_head is not None and n_kv_head != n_head:
+        if n_kv_head < 1 or n_head % n_kv_head or qkv.shape[-1] % (n_head + 2 * n_kv_head):
+            raise ValueError(f"causal_attention: n_kv_head={n_kv_head} must divide n_head={n_head}, and the projection "
+                             f"be (n_head + 2 n_kv_head) D wide, got {tuple(qkv.shape)}")
+        if _hip_bf16(qkv) and qkv.shape[-1] // (n_head + 2 * n_kv_head) == 64:
+            return _FlashAttnGqaFn.apply(qkv, n_head, n_kv_head, 1.0 / math.sqrt(64), *(() if drop is None else (drop,)))
+        return causal_attention(expand_gqa(qkv, n_head, n_kv_head), n_head, drop)
     B, S, C3 = qkv.shape
     C = C3 // 3
     D = C // n_head

@@ -18,7 +18,7 @@ tokens and lengths are those of the eager call bit for bit.
 A session (the static token / out / done / length buffers, the KV caches with their counters, the graph) stays on the
 engine as ``engine.decode_session``; at most one. The next call with the same key, (B, total width, temperature,
 top_k, top_p, seed, sample0, eos, pad, repetition_penalty, no_repeat_ngram_size, logprobs, kv_dtype, the parameters'
-storage addresses),
+storage addresses, n_kv_head),
 replays it without capturing again; any
 other key replaces it. The weights are read in place, so optimizer steps between two calls need no new capture as long
 as the storages stay. ``engine.decode_graph_captures`` counts the captures.
@@ -116,7 +116,8 @@ def generate_graphed(engine, prompts, lens_host, new: int, sampling: Sampling, c
     B, total = prompts.shape[0], prompts.shape[1] + new
     sp = replace(sampling, temperature=float(sampling.temperature), top_k=int(sampling.top_k),
                  top_p=float(sampling.top_p), sample0=int(sampling.sample0))
-    key = (B, total) + astuple(sp)[1:] + (kv_dtype, _param_addresses(engine))
+    n_kv_head = engine.stages[min(engine.stages)].cfg.kv_heads  # (a grouped model's caches have other shapes)
+    key = (B, total) + astuple(sp)[1:] + (kv_dtype, n_kv_head, _param_addresses(engine))
     stage_ids = sorted(engine.stages)
     with eval_stages([engine.stages[s] for s in stage_ids]):
         ses = engine.decode_session

@@ -376,6 +376,21 @@ def _check_kv_dtype(kv_dtype, lookup: int, num_samples: int, num_beams: int, pre
             raise ValueError(f"generate: kv_dtype={kv_dtype!r} is not supported with {what}")
 
 
+def _check_grouped(cfg, lookup: int, num_samples: int, num_beams: int, prefill_chunk: int, kv_dtype: str):
+    """The refusals of a model with ``n_kv_head != n_head`` (grouped-query attention): the plain loop and
+    ``graph=True`` serve its cache."""
+    if not getattr(cfg, "grouped", False):
+        return
+    for on, what in ((lookup > 0, "lookup > 0 (the verify step's attention reads one kv head per query head)"),
+                     (num_samples > 1, "num_samples > 1 (the fork's attention reads one kv head per query head)"),
+                     (num_beams > 1, "num_beams > 1 (the beams' caches are forks)"),
+                     (prefill_chunk > 0, "prefill_chunk > 0 (the extend attention reads one kv head per query head)"),
+                     (kv_dtype != "bf16", f"kv_dtype={kv_dtype!r} (the fp8 / fp4 decode kernels read one kv head per "
+                                          "query head)")):
+        if on:
+            raise ValueError(f"generate: n_kv_head={cfg.n_kv_head} != n_head={cfg.n_head} is not supported with {what}")
+
+
 def _check_penalty(repetition_penalty, no_repeat_ngram_size, return_logprobs, lookup: int = 0, num_beams: int = 1):
     """The refusals of ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``return_logprobs``; returns the three as
     ``Sampling``'s last fields."""
@@ -528,6 +543,7 @@ def generate(engine, prompts, max_new_tokens: int, temperature: float = 0.0, top
     _check_beams(engine, cfg, prompts.shape[0], num_beams, temperature, top_k, top_p, num_samples,
                  graph, lookup, prefill_chunk)
     _check_kv_dtype(kv_dtype, lookup, num_samples, num_beams, prefill_chunk)
+    _check_grouped(cfg, lookup, num_samples, num_beams, prefill_chunk, kv_dtype)
     if graph:
         check_graph(engine, cfg)
     sp = Sampling(cfg.vocab_size, temperature, top_k, top_p, dropout_seed(0 if seed is None else seed), sample0,

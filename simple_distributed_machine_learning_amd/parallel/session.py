@@ -80,6 +80,9 @@ class GenerationSession:
             raise ValueError(f"GenerationSession: pp={mesh.pp} is not supported (the caches of a session live on one "
                              "rank); run one rank")
         prompts, cfg = _check(engine, prompts, 0)  # tp, dp, rotate, a decode path, the prompts' form
+        if getattr(cfg, "grouped", False):
+            raise ValueError(f"GenerationSession: n_kv_head={cfg.n_kv_head} != n_head={cfg.n_head} is not supported (a "
+                             "session appends and extends its caches, which a grouped cache does not serve yet)")
         max_len = int(max_len)
         if max_len > cfg.block_size:
             raise ValueError(f"GenerationSession: max_len {max_len} exceeds block_size={cfg.block_size}")

@@ -62,6 +62,7 @@ def make_datasets(args, spec, device):
 def run(args) -> dict:
     cli.export_env(args)
     pdrop = {k: getattr(args, k, 0.0) for k in GPT2_DROPOUT_FLAGS}
+    n_kv_head = getattr(args, "n_kv_head", None)
     device = _device(args)
     stages = args.stages or DEFAULT_STAGES[args.model]
     tp = max(1, getattr(args, "tp", 1))
@@ -81,7 +82,7 @@ def run(args) -> dict:
     kw = {"dtype": dt} if dt is not None and args.model in ("resnet18", "gpt2_tiny") else {}
     try:
         spec = get_model_spec(args.model, stages, eval_dropout=bool(args.eval_dropout), seq_len=args.seq_len,
-                              dropout=getattr(args, "dropout", 0.5), **pdrop, **kw)
+                              dropout=getattr(args, "dropout", 0.5), n_kv_head=n_kv_head, **pdrop, **kw)
         if dt is not None and spec.param_dtype != dt:
             raise SystemExit(f"--dtype {args.dtype} is not supported for --model {args.model}")
         engine = PipelineEngine(spec, mesh, schedule_kind=args.schedule, num_microbatches=args.microbatches,
@@ -93,8 +94,9 @@ def run(args) -> dict:
                                 lr_schedule=cli.lr_schedule_of(args) if hasattr(args, "lr_schedule") else None)
     except ValueError as e:
         # GPT-2 dropout with another model is refused by the model registry, with --schedule rotate by the engine
-        # (every rank alike): end with their message instead of a traceback
-        if not any(pdrop.values()):
+        # (every rank alike): end with their message instead of a traceback. --n_kv_head likewise: another model, a
+        # value that does not divide the heads, --tp > 1
+        if not any(pdrop.values()) and n_kv_head is None:
             raise
         raise SystemExit(str(e))
     torch.manual_seed(args.seed * 7 + mesh.rank)  # dropout streams (reference: unseeded)
@@ -111,6 +113,8 @@ def run(args) -> dict:
             print("[sdml] GPT-2 dropout, effective probabilities: " + ", ".join(f"{k}={v:.6f}" for k, v in eff.items()),
                   flush=True)
         metrics.log(event="config", model=args.model, **eff)
+    if n_kv_head is not None:
+        metrics.log(event="config", model=args.model, n_kv_head=n_kv_head)
     B = args.batch_size
     GB = B * engine.data_shards  # one optimizer step consumes this many samples
     TB = args.test_batch_size or B

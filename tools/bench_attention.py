@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--fwd_kb", type=int, default=0, help="forward keys per tile (0 = default)")
     ap.add_argument("--attn_pdrop", type=float, default=0.0, help="also time the kernels with attention dropout")
     ap.add_argument("--rounds", type=int, default=3, help="alternated p = 0 / p > 0 timing rounds (--attn_pdrop)")
+    ap.add_argument("--n_kv_head", type=int, default=None,
+                    help="also time the three kernels with this many key/value heads against n_kv_head = H, alternated")
     a = ap.parse_args()
     B, H, S, D = a.B, a.H, a.S, 64
     dev = torch.device("cuda", 0)
@@ -82,6 +84,29 @@ def main():
                 rounds[name + "_p0"].append(round(timeit(bwd(parts, False)), 1))
                 rounds[name + "_drop"].append(round(timeit(bwd(parts, True)), 1))
         drop = {"attn_pdrop_effective": T / 256.0, "alternated_us": rounds}
+    if a.n_kv_head is not None:  # grouped-query attention: the three kernels, n_kv_head = H against the grouped call
+        Hkv = a.n_kv_head
+        gqkv = torch.randn(B, S, (H + 2 * Hkv) * D, device=dev, dtype=torch.bfloat16)
+        dgqkv = torch.empty_like(gqkv)
+
+        def views(t):
+            x, y, z = t.split((H * D, Hkv * D, Hkv * D), dim=-1)
+            return x.view(B, S, H, D), y.view(B, S, Hkv, D), z.view(B, S, Hkv, D)
+
+        gout, glse = K.attention_fwd(*views(gqkv), scale, True)
+        delta, gdelta = torch.empty_like(lse), torch.empty_like(glse)
+        calls = {"fwd_mha": lambda: K.attention_fwd(q, k, v, scale, True),
+                 "fwd_gqa": lambda: K.attention_fwd(*views(gqkv), scale, True)}
+        for name, parts in (("dq", 1), ("dkdv", 2)):
+            calls[name + "_mha"] = lambda parts=parts: K.attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, scale, True,
+                                                                      parts=parts, delta=delta)
+            calls[name + "_gqa"] = lambda parts=parts: K.attention_bwd(*views(gqkv), gout, dout, glse, *views(dgqkv),
+                                                                      scale, True, parts=parts, delta=gdelta)
+        rounds = {n: [] for n in calls}
+        for _ in range(a.rounds):
+            for n, fn in calls.items():  # alternated
+                rounds[n].append(round(timeit(fn), 1))
+        drop["gqa"] = {"n_kv_head": Hkv, "alternated_us": rounds}
     qt, kt, vt = (x.transpose(1, 2).contiguous().requires_grad_(True) for x in (q, k, v))
     t_sf = timeit(lambda: F.scaled_dot_product_attention(qt, kt, vt, is_causal=True))
     y = F.scaled_dot_product_attention(qt, kt, vt, is_causal=True)

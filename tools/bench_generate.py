@@ -752,8 +752,84 @@ def main_rows(a):
     return 0 if ok else 1
 
 
+# ---- grouped-query attention (--n_kv_head) ----------------------------------------------------------------------------
+def bench_gqa_kernels(Hkv, rounds, reps, emit):
+    """attention_decode at H = 12 against the grouped kernel on a cache of Hkv heads, both launches, alternated."""
+    K = _native.kernels()
+    H, D = 12, 64
+    for B, ctx in ((64, 1024), (64, 512), (16, 512)):
+        Smax = ctx + 1
+        lens = torch.full((B,), ctx, dtype=torch.int32, device=DEV)
+        fns, nbytes = {}, {}
+        for name, heads in (("attention_decode", H), ("attention_decode_gqa", Hkv)):
+            nbytes[name] = B * Smax * heads * D * 2 * 2
+            copies = max(2, min(reps, LLC_BYTES // nbytes[name] + 1))
+            kc = torch.randn(copies, B, Smax, heads, D, device=DEV, dtype=BF)
+            vc = torch.randn(copies, B, Smax, heads, D, device=DEV, dtype=BF)
+            qkv = torch.randn(B, (H + 2 * heads) * D, device=DEV, dtype=BF)
+            if heads == H:
+                fns[name] = lambda i, a=(qkv, kc, vc, copies): K.attention_decode(a[0], a[1][i % a[3]], a[2][i % a[3]],
+                                                                                  lens, 0.125, Smax)
+            else:
+                fns[name] = lambda i, a=(qkv, kc, vc, copies): K.attention_decode_gqa(
+                    a[0], a[1][i % a[3]], a[2][i % a[3]], lens, H, 0.125, Smax)
+            window(fns[name], copies)
+        for r in range(rounds):
+            for name, fn in fns.items():  # alternated
+                ms = window(fn, reps)
+                emit({"kernel": name, "B": B, "H": H, "n_kv_head": H if name == "attention_decode" else Hkv,
+                      "ctx": ctx, "round": r, "us": round(ms * 1e3, 2), "bytes": nbytes[name],
+                      "GB_per_s": round(nbytes[name] / (ms * 1e-3) / 1e9, 1)})
+        del fns
+        torch.cuda.empty_cache()
+
+
+@torch.no_grad()
+def bench_gqa_loop(engines, B, ctx, steps, rounds, emit):
+    """Tokens/s of the decode loop, n_kv_head = n_head against the grouped model, eager and graph-replayed."""
+    forms = [(name, g) for g in (False, True) for name in engines]
+    ses = {}
+    for name, g in forms:
+        if g:
+            ses[name] = DecodeSession(engines[name], None, B, ctx + steps)
+            ses[name].capture(engines[name], SAMPLING)
+        run_kv_loop(engines[name], B, ctx, 8, "bf16", ses.get(name) if g else None)
+    for r in range(rounds):
+        for name, g in forms:  # alternated
+            s = run_kv_loop(engines[name], B, ctx, steps, "bf16", ses[name] if g else None)
+            emit({"loop": f"n_kv_head={name} {'graph' if g else 'eager'}", "B": B, "ctx": ctx, "steps": steps,
+                  "round": r, "ms_per_step": round(s / steps * 1e3, 4), "tokens_per_s": round(B * steps / s, 1)})
+    del ses
+    torch.cuda.empty_cache()
+
+
+def main_gqa(a):
+    os.makedirs(os.path.dirname(a.out_gqa) or ".", exist_ok=True)
+    with open(a.out_gqa, "w") as f:
+        def emit(rec):
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+
+        if not a.no_kernels:
+            bench_gqa_kernels(a.n_kv_head, a.rounds, a.reps, emit)
+        mesh = init_mesh(pp=1, schedule_kind="1f1b", rank=0, world_size=1, device=DEV)
+        engines = {}
+        for hkv in (12, a.n_kv_head):
+            engines[hkv] = PipelineEngine(get_model_spec("gpt2", 2, n_kv_head=hkv), mesh, schedule_kind="1f1b",
+                                          num_microbatches=1)
+            engines[hkv].eval()
+        bench_gqa_loop(engines, a.B, min(a.ctx, 1024 - a.steps), a.steps, a.rounds, emit)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--n_kv_head", type=int, default=None,
+                    help="only grouped-query attention: attention_decode at H = 12 against the grouped kernel with this "
+                         "many kv heads, and the decode loops of both models, written to --out_gqa")
+    ap.add_argument("--out_gqa", default="profiles/generate_gqa.jsonl")
     ap.add_argument("--rows", action="store_true",
                     help="only linear_rows: its windows against gemm_bf16 at 65..512 rows and the decode loops at B > 64")
     ap.add_argument("--out_rows", default="profiles/linear_rows.jsonl")
@@ -779,6 +855,8 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py measures on the GPU; none is visible")
+    if a.n_kv_head is not None:
+        return main_gqa(a)
     if a.rows:
         return main_rows(a)
     if a.kv_dtype in ("fp8", "fp4"):
